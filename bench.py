@@ -2,7 +2,15 @@
 of N=1024 points per GPU, on the MI355X-native SA path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ssg|msg|pose|stress|v1]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line with `value` and
+`ms_per_step`; value_settled and the fields from value_fused down are measured only with --full
+(runs of their own after the headline) and are null without it.  --dump-outputs DIR writes what the last timed
+step returned -- every head's gathered first output, DIR/<head>.npy -- so that two builds can be
+compared output for output: inputs, weights and FPS start draws are seeded, the same arguments
+give the same step.
 
 One step = one forward of the head over every rank's batch shard (weak scaling: B clouds per
 GPU, global batch = B*N) followed by the RCCL all_gather of the logits -- the only exchange the
@@ -97,6 +105,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)  # pipelined: K batches in one pass, fill amortised
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="ssg", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry: "
+                         "value_settled, value_fused, eager_value, eager_value_reference_head, "
+                         "roofline / roofline_ball_query / kernels and cpu_baseline (each with "
+                         "its own --no-... switch); without it they are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (every head's gathered first "
+                         "output) as DIR/<head>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound on the CPU baseline sample")
     ap.add_argument("--no-kernel-timer", action="store_true")
@@ -293,6 +309,26 @@ def load_mfma_busy(cfg):
             "source": "profiles/sq_mfma.json (SQ_VALU_MFMA_BUSY_CYCLES, eager launch)"}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(d, names, outs):
+    """--dump-outputs: every head's gathered first output of the last timed step (what step()
+    returns to its caller) as d/<head>.npy, float32 (float64 if the head returns that).  A head
+    whose output exceeds its share of DUMP_BYTES is written as a fixed seeded sample of its
+    flattened elements, so two builds are still compared element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(outs)
+    for n, o in zip(names, outs):
+        arr = o.detach().cpu().numpy()
+        arr = arr.astype(np.float64 if arr.dtype == np.float64 else np.float32)
+        if arr.nbytes > share:
+            keep = np.random.default_rng(0).choice(arr.size, share // arr.itemsize, replace=False)
+            arr = arr.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(d, n + ".npy"), arr)
+
+
 def count_gpus(topology="/sys/class/kfd/kfd/topology/nodes"):
     """GPUs this process may use, counted without initialising HIP: the KFD topology's GPU
     nodes (simd_count > 0), capped by HIP_/ROCR_/CUDA_VISIBLE_DEVICES.  The launcher's parent
@@ -474,14 +510,16 @@ def main():
         return o[0] if isinstance(o, tuple) else o
 
     def run_pipelined(k, pf_=None):
+        """k batches through the pipeline; returns the last batch's gathered outputs."""
         pf_ = pf_ or pf
         with shard.batch_shard(gB, lo):
             if a.gather_every > 1:  # one collective per gather_every batches (DESIGN.md §6)
                 bg = shard.BatchedGather(a.gather_every, total=k)
                 post = lambda i, o: bg(i, first_outputs(o))  # noqa: E731
             else:
-                post = gather
-            pf_.run([x] * k, [(mean,)] * k if takes_mean else None, post=post)
+                bg, post = None, gather
+            outs = pf_.run([x] * k, [(mean,)] * k if takes_mean else None, post=post)
+        return bg.results[-1] if bg is not None else outs[-1]
 
     for _ in range(max(a.warmup, 2) if a.graph else a.warmup):  # graph: 1st call captures
         step(names, models, x, mean, gB, lo)
@@ -498,9 +536,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None  # what the last step returned
         if pipe:
             kt = None
-            run_pipelined(k, pipe if pipe is not True else None)
+            last = run_pipelined(k, pipe if pipe is not True else None)
         elif timer:
             with ops.kernel_timer() as kt:
                 for _ in range(k):
@@ -509,12 +548,12 @@ def main():
         else:
             kt = None
             for _ in range(k):
-                step(names, models, x, mean, gB, lo)
+                last = step(names, models, x, mean, gB, lo)
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         if world > 1:
             dist.barrier()
-        return el, kt
+        return el, kt, last
 
     def max_over_ranks(el):
         t = torch.tensor([el], dtype=torch.float64, device=dev)
@@ -522,20 +561,24 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    el, _ = timed(a.steps, False, pipe=pipelined)
+    el, _, last = timed(a.steps, False, pipe=pipelined)
     el = max_over_ranks(el)
     ms = el / a.steps * 1e3
     value = gB * a.steps / el
-    eager_value = value
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, names, last if isinstance(last, list) else [last])
+    del last
+    # Everything below the headline is --full's: a plain run prints the line now
+    eager_value = None if a.graph or pipelined else value
     # The same K batches again once the device has been busy for a while (untimed pipelined
     # batches for ~80 ms first): after an idle gap the SOC clock sits in deep sleep (38-47 MHz)
     # and needs ~30 ms of load to reach 1200 MHz, and a pipelined run at a low SOC clock is up
     # to 25 % slower (tools/debug/clock_trace.py).  `value` above is the
     # contract's number (W warm-up steps, then K timed); this one is reported beside it.
     settled = None
-    if pipelined and not a.no_settled:
+    if a.full and pipelined and not a.no_settled:
         run_pipelined(max(a.steps, int(80.0 / max(ms, 1e-3)) + 1))
-        el_s, _ = timed(a.steps, False, pipe=True)
+        el_s, _, _ = timed(a.steps, False, pipe=True)
         el_s = max_over_ranks(el_s)
         settled = {"value": round(gB * a.steps / el_s, 2), "ms_per_step": round(el_s / a.steps * 1e3, 4),
                    "settle": "~80 ms of untimed pipelined batches before the same K timed steps"}
@@ -544,40 +587,40 @@ def main():
     # serving mode with launch batch fused_batches x B, bit-equal per batch to the eager forward
     # (tests/test_gpu_configs.py), reported beside the headline, never as it.
     fused = None
-    if pipelined and not a.eager_pipeline and a.fused_batches > 1 and (
+    if a.full and pipelined and not a.eager_pipeline and a.fused_batches > 1 and (
             a.fuse is False or a.geometry_batches != a.fused_batches):
         pf4 = graphed(a.fused_batches, True)
         run_pipelined(max(a.warmup, 2), pf4)
         run_pipelined(max(a.steps, int(80.0 / max(ms, 1e-3)) + 1), pf4)
-        el_f, _ = timed(a.steps, False, pipe=pf4)
+        el_f, _, _ = timed(a.steps, False, pipe=pf4)
         el_f = max_over_ranks(el_f)
         fused = {"value": round(gB * a.steps / el_f, 2), "ms_per_step": round(el_f / a.steps * 1e3, 4),
                  "launch_batch": a.fused_batches * (hi - lo), "geometry_batches": a.fused_batches,
                  "launch": "graphed pipeline; %d consecutive batches per launch (FPS, ball queries, "
                            "MLPs, head), after ~80 ms of untimed batches" % a.fused_batches}
         del pf4
-    if a.graph or pipelined:
+    if a.full and (a.graph or pipelined):
         # the eager pass's own warm-up: after the pipelined runs (whose graphs keep private
         # memory pools) the first eager forwards allocate afresh
         for _ in range(3):
             step(names, eager_models, x, mean, gB, lo)
-        el_e, _ = timed(a.steps, False, eager_models)
+        el_e, _, _ = timed(a.steps, False, eager_models)
         eager_value = gB * a.steps / max_over_ranks(el_e)
     # The unchanged reference head through the drop-in: its forward restated call for call
     # (pn2.heads.ReferenceForward -- SA modules one after the other, no FPS side job, the torch
     # FC tail), eager, the same K steps
     ref_value = None
-    if not a.no_reference_head:
+    if a.full and not a.no_reference_head:
         from pn2 import heads as _heads
         if all(n in _heads.HEADS for n in names):
             ref_models = [_heads.ReferenceForward(m) for m in eager_models]
             for _ in range(3):
                 step(names, ref_models, x, mean, gB, lo)
-            el_r, _ = timed(a.steps, False, ref_models)
+            el_r, _, _ = timed(a.steps, False, ref_models)
             ref_value = round(gB * a.steps / max_over_ranks(el_r), 2)
     kt = None
-    if not a.no_kernel_timer:
-        _, kt = timed(a.steps, True, eager_models)
+    if a.full and not a.no_kernel_timer:
+        _, kt, _ = timed(a.steps, True, eager_models)
 
     kern = kt.summary() if kt is not None else {}
     mlp_name = "pn2_sa_mlp_max_bf16" if prec == "bf16" else "pn2_sa_mlp_max_f32"
@@ -640,7 +683,7 @@ def main():
                    "avg_launch_ms": bq["ms"] / bq["launches"]}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "ssg":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "ssg":
         cpu = cpu_baseline(a.cpu_seconds)
 
     if rank == 0:
@@ -678,7 +721,7 @@ def main():
                                "; ball queries in each batch's forward" if pf.geometry_bq is False else ""))
                            if not a.eager_pipeline else "")
                        if pipelined else "eager"),
-            "eager_value": round(eager_value, 2),
+            "eager_value": None if eager_value is None else round(eager_value, 2),
             "eager_value_reference_head": ref_value,
             "value_fused": fused,
             "value_settled": settled,

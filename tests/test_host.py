@@ -238,6 +238,43 @@ def test_count_gpus_without_hip(monkeypatch, tmp_path):
     assert bench.count_gpus(str(tmp_path / "absent")) == 0
 
 
+def test_bench_plain_run_is_the_default(monkeypatch):
+    """Without --full the benchmark measures the headline only; --dump-outputs is off."""
+    sys.path.insert(0, os.path.dirname(PKG))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one <head>.npy per head in float32 (float64 kept), whole while it fits the
+    byte budget, else the same seeded sample of the flattened output in every run."""
+    sys.path.insert(0, os.path.dirname(PKG))
+    import bench
+    h1 = torch.arange(12, dtype=torch.float32).reshape(3, 4) / 7
+    h2 = torch.arange(12, dtype=torch.float64).reshape(3, 4) / 3
+    bench.dump_outputs(str(tmp_path / "a"), ["h1", "h2"], [h1, h2])
+    g1, g2 = np.load(tmp_path / "a" / "h1.npy"), np.load(tmp_path / "a" / "h2.npy")
+    assert g1.dtype == np.float32 and g2.dtype == np.float64
+    np.testing.assert_array_equal(g1, h1.numpy())
+    np.testing.assert_array_equal(g2, h2.numpy())
+    bench.dump_outputs(str(tmp_path / "i"), ["h"], [torch.arange(6).reshape(2, 3)])
+    assert np.load(tmp_path / "i" / "h.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64)  # 32 bytes per head: 8 float32 / 4 float64
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), ["h1", "h2"], [h1, h2])
+    s1, s2 = np.load(tmp_path / "b" / "h1.npy"), np.load(tmp_path / "b" / "h2.npy")
+    assert s1.shape == (8,) and s2.shape == (4,)
+    assert s1.nbytes + s2.nbytes <= 64
+    assert set(s1.tolist()) <= set(g1.ravel().tolist()) and len(set(s1.tolist())) == 8
+    np.testing.assert_array_equal(s1, np.load(tmp_path / "c" / "h1.npy"))
+    np.testing.assert_array_equal(s2, np.load(tmp_path / "c" / "h2.npy"))
+
+
 def shard_ranges(B, world):
     sys.path.insert(0, PKG)
     from pn2 import shard

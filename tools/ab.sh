@@ -36,7 +36,7 @@ for r in $(seq 1 $rounds); do
     case "$MODE" in
       bench|eager)
         extra=""; [ "$MODE" = eager ] && extra="--no-pipeline --no-reference-head"
-        timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} $base $extra $args > $OUT/b_${tag}_$r.log 2>&1 \
+        timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} $base $extra $args > $OUT/b_${tag}_$r.log 2>&1 \
           || { echo "[$v] rc=$?"; tail -5 $OUT/b_${tag}_$r.log; exit 1; }
         python -c "import json; d=json.loads([l for l in open('$OUT/b_${tag}_$r.log') if l.startswith('{')][-1]); print('%-48s round $r: value %9.1f  eager %9.1f  ref-head %s' % ('[$v]', d['value'], d['eager_value'], d.get('eager_value_reference_head')))"
         ;;

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT}"
 mkdir -p gpurun_out/ab
-F=${BENCH_FLAGS:-"--steps 20 --warmup 5 --no-cpu-baseline --fused-batches 0 --no-reference-head --no-kernel-timer"}
+F=${BENCH_FLAGS:-"--full --steps 20 --warmup 5 --no-cpu-baseline --fused-batches 0 --no-reference-head --no-kernel-timer"}
 for i in $(seq 1 ${REPS:-2}); do
   for v in ${VARIANTS}; do
     d=_ab/$v; [ "$v" = "." ] && d=.

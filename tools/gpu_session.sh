@@ -22,7 +22,7 @@ if [ -n "${KT:-}" ]; then
     tag=${kv%%:*}; tun=${kv#*:}
     rm -rf $OUT/kt_$tag
     if [ -n "$tun" ]; then export PN2_TUNING="$tun"; else unset PN2_TUNING; fi
-    timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/kt_$tag -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timer --no-pipeline ${BENCH_ARGS:-} > $OUT/kt_$tag.log 2>&1
+    timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/kt_$tag -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timer --no-pipeline ${BENCH_ARGS:-} > $OUT/kt_$tag.log 2>&1
     rc=$?; unset PN2_TUNING; [ $rc -ne 0 ] && { echo "kt $tag rc=$rc"; tail -5 $OUT/kt_$tag.log; exit $rc; }
     python tools/kstats.py $OUT/kt_$tag > $OUT/kstats_$tag.txt
     echo "== eager $tag"; head -14 $OUT/kstats_$tag.txt

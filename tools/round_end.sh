@@ -13,10 +13,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
 step $? pytest; tail -2 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 step $? smoke; tail -2 $OUT/smoke.log
-timeout -k 10 600 python bench.py > $OUT/bench_default.log 2>&1
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.log 2>&1
 step $? bench_default; grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20_$i.log 2>&1
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20_$i.log 2>&1
   step $? bench_k20_$i; grep '^{' $OUT/bench_k20_$i.log | tail -1 > $OUT/bench_k20_$i.json
 done
 python - <<'PY'
@@ -27,10 +27,10 @@ for f in ["bench_default"] + ["bench_k20_%d" % i for i in (1, 2, 3)]:
           d.get("eager_value"), d["roofline"]["frac"], (d.get("cpu_baseline") or {}).get("value"))
 PY
 rm -rf $OUT/prof_pipe $OUT/prof_eager
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_pipe -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-timer > $OUT/prof_pipe.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_pipe -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-timer > $OUT/prof_pipe.log 2>&1
 step $? prof_pipe
 cp $(find $OUT/prof_pipe -name "*kernel_stats.csv" | head -1) $OUT/pipelined_kernel_stats.csv
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_eager -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timer --no-pipeline > $OUT/prof_eager.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_eager -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timer --no-pipeline > $OUT/prof_eager.log 2>&1
 step $? prof_eager
 cp $(find $OUT/prof_eager -name "*kernel_stats.csv" | head -1) $OUT/eager_kernel_stats.csv
 python tools/kstats.py $OUT/prof_eager > $OUT/kstats_eager.txt
