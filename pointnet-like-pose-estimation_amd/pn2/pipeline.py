@@ -13,7 +13,7 @@ B=32, which is longer than the compute stream's work once the MLP kernels are fa
 
 CUs.  By default (geometry_cus=0) the streams are ordinary streams sharing every CU, geometry
 at high priority.  ``geometry_cus > 0`` gives the geometry stream its own CUs instead
-(hipExtStreamCreateWithCUMask through pn2_stream_create_cu_masked; see ``_streams`` for how
+(hipExtStreamCreateWithCUMask through pn2_stream_create_cu_masked; see ``_StreamSet`` for how
 MI355X maps mask bits to XCDs).  Measured, SSG B=32 N=1024, graphed: shared 69.5k / 69.9k
 clouds/s; 8 dedicated CUs (1 per XCD) 65.0k / 65.1k; 24 CUs 63.3k / 64.4k -- FPS co-resident
 with the MFMA kernels costs the chains less than the CUs a partition withholds from them.
@@ -44,6 +44,7 @@ previous layer's centroids (every reference head).  Inputs must be ready on the 
 stream when ``run`` is called.
 """
 import atexit
+import collections
 import ctypes
 import contextlib
 import os
@@ -57,22 +58,6 @@ from . import ops
 from . import shard
 from . import tuning
 from .pointnet2_utils import PointNetSetAbstraction, PointNetSetAbstractionMsg, msg_ball_queries
-
-_partitions = {}  # (device, geometry CUs) -> (geometry, compute, tail streams, raw handles)
-
-
-@atexit.register
-def _destroy_partitions():
-    """Release the CU-masked streams before the HIP runtime tears down (left to process exit,
-    their destruction raced the runtime's own teardown under rocprofv3)."""
-    for key, (*_, raw) in list(_partitions.items()):
-        try:
-            torch.cuda.synchronize(key[0])
-        except Exception:
-            pass
-        for h in raw:
-            _lib.load().pn2_stream_destroy(h)
-    _partitions.clear()
 
 
 def _cu_count(device):
@@ -92,16 +77,7 @@ def _masked_stream(device, cus, ncu):
     return torch.cuda.ExternalStream(ptr.value, device=torch.device("cuda", device)), ptr.value
 
 
-# hipExtStreamCreateWithCUMask on MI355X (measured, tools/micro/cu_mask_map.hip): mask bit i
-# belongs to XCD i % 8 and selects CU i / 8 of it, and an XCD whose share of the mask is empty
-# is NOT restricted (all 32 of its CUs run the stream).  So a partition is a contiguous block of
-# bits: [0, g) = g/8 CUs on every XCD, [g, 256) = the other CUs of every XCD.  (A mask spread
-# with stride 8 -- bits 0, 8, 16, ... -- is XCD 0 alone plus the seven unrestricted XCDs: the
-# whole chip.)
 _XCDS = 8
-
-
-_extra = {}  # device -> (second geometry stream, second compute stream)
 
 
 def _hw_queues():
@@ -112,88 +88,112 @@ def _hw_queues():
         return 4
 
 
-def _streams(device, geometry_cus):
-    key = (device, geometry_cus)
-    if key not in _partitions and int(geometry_cus) <= 0:
-        # no partition: ordinary streams sharing every CU, geometry at high priority.  A HIP
-        # stream is bound to one of the process's hardware queues at its first command (up to
-        # GPU_MAX_HW_QUEUES = 4 per priority; past that, the least-used one).  Which queue a
-        # pipeline stream lands on changed the throughput by up to 45 % (SSG, rocprofv3
-        # Queue_Id per dispatch, tools/debug/gpipe_events.py): with the default stream's queue
-        # first, the streams first used second and third ran at full speed, while a stream on
-        # the fourth queue fell behind -- the tail stream there took 570-800 us per head
-        # instead of 130-300 (58-65k clouds/s), the second compute stream there cost ~8 %
-        # (97-100k), and a stream first used late (after the captures' streams) shared another
-        # pipeline stream's queue (84-87k).  So the geometry, first compute and tail streams
-        # each run one tiny command here, in that order, and the second compute stream is the
-        # default stream itself, whose queue exists from the start: 103-106k at any slot count.
-        dev = torch.device("cuda", device)
-        lo, hi = torch.cuda.Stream.priority_range()
-        geo = torch.cuda.Stream(dev, priority=min(lo, hi))
-        geo2 = torch.cuda.Stream(dev, priority=min(lo, hi))
-        main = torch.cuda.Stream(dev)
-        # tuning tail_prio = 1: the tail (heads) at high priority as well (A/B)
-        tail = torch.cuda.Stream(dev, priority=min(lo, hi) if tuning.get("tail_prio") else 0)
-        main2 = torch.cuda.default_stream(dev)
-        tail2 = torch.cuda.Stream(dev, priority=min(lo, hi) if tuning.get("tail_prio") else 0)
-        # one more normal-priority stream, never used: creating it moves the hardware queues
-        # the later geometry streams (_extra_geometry_streams) get, and without it the headline
-        # pipeline loses 15-25 % (r06, same box, interleaved: K = 20 117-122k with it, 88-99k
-        # without; tools/ab_worktree.sh)
-        spare = torch.cuda.Stream(dev)
-        for st in (geo, main, tail):
-            with torch.cuda.stream(st):
-                torch.zeros(1, device=dev)
-            st.synchronize()
-        _partitions[key] = (geo, main, tail, ())
-        _extra[device] = (geo2, main2, tail2, spare)
-    if key not in _partitions:
+def _high_stream(dev):
+    return torch.cuda.Stream(dev, priority=min(torch.cuda.Stream.priority_range()))
+
+
+def _touch(st):
+    """One tiny command and a synchronise on `st`: a HIP stream is bound to one of the
+    process's hardware queues at its first command."""
+    with torch.cuda.stream(st):
+        torch.zeros(1, device=st.device)
+    st.synchronize()
+
+
+class _StreamSet:
+    """The pipeline streams of one device: ``geo``, ``compute`` and ``tails`` (lists; a pipeline
+    takes the first n of each), cached per (device, geometry CUs) by ``_stream_set``.
+
+    Shared CUs (geometry_cus <= 0): ordinary streams sharing every CU.  The ORDER in which they
+    are created and first used is part of the contract -- the headline depends on it by
+    15-25 % -- and it is:
+      created: geometry 1 (high priority), geometry 2 (high priority), compute 1, tail 1,
+               compute 2 (the device's default stream, not a new one), tail 2, and a spare
+               stream that is never used;
+      then one tiny command and a synchronise on geometry 1, compute 1, tail 1, in that order;
+      geometry 3 and 4 (high priority) only when a pipeline first asks for them (``_stream_set``),
+      each touched the same way at creation.
+    Why: a HIP stream is bound to one of the process's hardware queues at its first command (up
+    to GPU_MAX_HW_QUEUES = 4 per priority; past that, the least-used one).  Which queue a
+    pipeline stream lands on changed the throughput by up to 45 % (SSG, rocprofv3 Queue_Id per
+    dispatch, tools/debug/gpipe_events.py): with the default stream's queue first, the streams
+    first used second and third ran at full speed, while a stream on the fourth queue fell
+    behind -- the tail stream there took 570-800 us per head instead of 130-300 (58-65k
+    clouds/s), the second compute stream there cost ~8 % (97-100k), and a stream first used
+    late (after the captures' streams) shared another pipeline stream's queue (84-87k).  Hence
+    the three touches, and the default stream, whose queue exists from the start, as the second
+    compute stream: 103-106k at any slot count.  The spare: creating it moves the hardware
+    queues the later geometry streams get, and without it the headline pipeline loses 15-25 %
+    (r06, same box, interleaved: K = 20 117-122k with it, 88-99k without;
+    tools/ab_worktree.sh).
+
+    CU-masked (geometry_cus > 0): one stream each, created in the order geometry, compute,
+    tail.  hipExtStreamCreateWithCUMask on MI355X (measured, tools/micro/cu_mask_map.hip): mask
+    bit i belongs to XCD i % 8 and selects CU i / 8 of it, and an XCD whose share of the mask is
+    empty is NOT restricted (all 32 of its CUs run the stream).  So a partition is a contiguous
+    block of bits: [0, g) = g/8 CUs on every XCD for the geometry and tail streams, [g, 256) =
+    the other CUs of every XCD for the compute stream.  (A mask spread with stride 8 -- bits 0,
+    8, 16, ... -- is XCD 0 alone plus the seven unrestricted XCDs: the whole chip.)  No
+    shared-CU stream is created for such a set; its ``raw`` handles are destroyed at exit."""
+
+    def __init__(self, device, geometry_cus):
+        self.raw = ()
+        if geometry_cus <= 0:
+            dev = torch.device("cuda", device)
+            self.geo = [_high_stream(dev), _high_stream(dev)]
+            self.compute = [torch.cuda.Stream(dev)]
+            self.tails = [torch.cuda.Stream(dev)]
+            self.compute.append(torch.cuda.default_stream(dev))
+            self.tails.append(torch.cuda.Stream(dev))
+            self.spare = torch.cuda.Stream(dev)
+            for st in (self.geo[0], self.compute[0], self.tails[0]):
+                _touch(st)
+            return
         ncu = _cu_count(device)
         per = max(1, min(int(geometry_cus) // _XCDS, ncu // _XCDS - 1))  # CUs per XCD
         geo = list(range(per * _XCDS))
         rest = list(range(per * _XCDS, ncu))
         (gs, gh), (cs, ch) = _masked_stream(device, geo, ncu), _masked_stream(device, rest, ncu)
         ts, th = _masked_stream(device, geo, ncu)
-        _partitions[key] = (gs, cs, ts, (gh, ch, th))
-    return _partitions[key][:3]
+        self.geo, self.compute, self.tails, self.raw = [gs], [cs], [ts], (gh, ch, th)
 
 
-_more_geo = {}  # device -> geometry streams past the second (GraphedPipeline(geometry_streams>2))
+_stream_sets = {}  # (device, geometry CUs) -> _StreamSet
 
 
-def _extra_geometry_streams(device, n):
-    """n (0-3) more high-priority streams for GraphedPipeline(geometry_streams=1+n) (shared
-    CUs; the second is created with the others by _streams, later ones on first use).  n = 0
-    touches no stream: with geometry_cus > 0 the shared-CU set would add queues beyond the
-    masked streams'."""
-    if n <= 0:
-        return []
-    _streams(device, 0)
-    more = _more_geo.setdefault(device, [])
-    while len(more) < n - 1:
-        lo, hi = torch.cuda.Stream.priority_range()
-        st = torch.cuda.Stream(torch.device("cuda", device), priority=min(lo, hi))
-        with torch.cuda.stream(st):
-            torch.zeros(1, device=torch.device("cuda", device))
-        st.synchronize()
-        more.append(st)
-    return ([_extra[device][0]] + more)[:n]
+def _stream_set(device, geometry_cus, geometry_streams=1):
+    """The device's _StreamSet, with at least `geometry_streams` geometry streams when the CUs
+    are shared (a masked set has its one)."""
+    key = (device, max(0, int(geometry_cus)))
+    if key not in _stream_sets:
+        _stream_sets[key] = _StreamSet(*key)
+    ss = _stream_sets[key]
+    while key[1] == 0 and len(ss.geo) < geometry_streams:
+        ss.geo.append(_high_stream(torch.device("cuda", device)))
+        _touch(ss.geo[-1])
+    return ss
 
 
-def _extra_compute_streams(device, n):
-    """n (0 or 1) more compute streams for GraphedPipeline(compute_streams=1+n) (created with
-    the others by _streams): the process's default stream."""
-    if n <= 0:
-        return []
-    _streams(device, 0)
-    return [_extra[device][1]][:n]
+@atexit.register
+def _destroy_stream_sets():
+    """Release the CU-masked streams before the HIP runtime tears down (left to process exit,
+    their destruction raced the runtime's own teardown under rocprofv3)."""
+    for (device, _), ss in list(_stream_sets.items()):
+        try:
+            torch.cuda.synchronize(device)
+        except Exception:
+            pass
+        for h in ss.raw:
+            _lib.load().pn2_stream_destroy(h)
+    _stream_sets.clear()
 
 
 def partition(device, geometry_cus):
     """(geometry stream, compute stream) on `device`: `geometry_cus` CUs (rounded down to a
     multiple of the XCD count, at least one per XCD) for the FPS chain, all the others for
     everything else.  Cached per (device, count)."""
-    return _streams(device, geometry_cus)[:2]
+    ss = _stream_set(device, geometry_cus)
+    return ss.geo[0], ss.compute[0]
 
 
 class PipelinedForward:
@@ -208,6 +208,8 @@ class PipelinedForward:
         self.geometry_cus = geometry_cus
         self.tail = tail
         self.sas = self._find_sas()
+        self.launch_batch = 128  # clouds per launch (_profile); GraphedPipeline.run sets it
+        self.geometry_bq = None  # ball queries on the geometry stream; None: tuning geometry_bq
 
     def _find_sas(self):
         return [m for m in self.model.modules()
@@ -262,7 +264,7 @@ class PipelinedForward:
         at one B=32 batch per launch: 104-112k vs 97-100k clouds/s with the profile, K = 20,
         interleaved x3; MSG flat).  Host key pipe_profile: 0 never, 2 always."""
         mode = int(tuning.get("pipe_profile"))
-        if mode == 2 or (mode == 1 and getattr(self, "launch_batch", 128) >= 64):
+        if mode == 2 or (mode == 1 and self.launch_batch >= 64):
             return tuning.pipeline_profile()
         return contextlib.nullcontext()
 
@@ -288,8 +290,7 @@ class PipelinedForward:
         entries = {}
         # geometry_bq = 0: the ball queries run in each batch's forward instead (the module
         # queries when its entry holds no lists), leaving the FPS alone on the geometry stream
-        gbq = getattr(self, "geometry_bq", None)
-        bq = bool(tuning.get("geometry_bq")) if gbq is None else bool(gbq)
+        bq = bool(tuning.get("geometry_bq") if self.geometry_bq is None else self.geometry_bq)
         pts = x.permute(0, 2, 1)
         first = {}  # chain -> (newp, cpk, ppk) of its first layer
         heads = [ch[0] for ch in chains]
@@ -332,7 +333,8 @@ class PipelinedForward:
         if not batches:
             return []
         dev = batches[0].device
-        geo, main, tail = _streams(dev.index, self.geometry_cus)
+        ss = _stream_set(dev.index, self.geometry_cus)
+        geo, main, tail = ss.geo[0], ss.compute[0], ss.tails[0]
         caller = torch.cuda.current_stream(dev)
         geo.wait_stream(caller)
         main.wait_stream(caller)
@@ -428,17 +430,67 @@ _MODE = "thread_local"
 
 class _Slot:
     """Static buffers and graphs of one batch slot: one batch of a geometry group, or the whole
-    group (``fused``)."""
-    fused = False
+    group (``fused``).  ``ev_head``: the slot's last head in the current run (the next forward
+    in the slot shares its memory pool and waits for it)."""
+    __slots__ = ("x", "extra", "sa", "head", "out", "sa_out", "tail_reads_geometry", "fused",
+                 "ev_head")
 
-
-class _Restart(Exception):
-    """An SA module was replaced between runs: the geometry graphs are stale (run() restarts)."""
+    def __init__(self):
+        self.fused = False
+        self.ev_head = None
 
 
 class _Group:
     """Static inputs and the geometry graph of ``geometry_batches`` consecutive batches; its
     ``halves`` are their batch slots."""
+    __slots__ = ("x", "start_buf", "fps", "entries", "B", "halves")
+
+
+_Unit = collections.namedtuple(
+    "_Unit", "group place slot batches compute tail fps_before fps_after")
+
+
+def _schedule(nbat, gb, ng, u, n_geo, n_compute, n_tails, drain):
+    """The issue order of ``GraphedPipeline.run`` as plain ints: one ``_Unit`` per forward.
+
+    nbat batches (counted after an eager first batch) in geometry groups of gb, on ng group
+    slots; a forward carries u consecutive batches (u = gb: fused group forwards, u = 1: one per
+    batch).  Unit k starts at batch b0 = k * u:
+      group, place, slot  b0 // gb, b0 % gb, group % ng: the forward replays
+                          ``_slots[slot].halves[place]``
+      batches             b0 .. min(b0 + u, nbat) - 1
+      compute             index of its compute stream: k % n_compute
+      tail                index of its head's tail stream, k % n_tails, or None: the head runs
+                          on the unit's own compute stream.  n_tails = 0 (no head graph, or no
+                          hardware queue left for a tail stream) puts every head there, and so
+                          do the last ceil(drain / u) units: the tail streams run ~2 heads
+                          behind the sa graphs, and at the end of a run that backlog is the
+                          drain, while the compute streams are idle by then
+      fps_before          (group, index of its geometry stream = group % n_geo) of every
+                          geometry group to issue before the forward: all not yet issued up to
+                          the unit's own
+      fps_after           at most one more after it, while it stays <= (group if the unit ends
+                          its group, else group - 1) + ng: group j takes the slot of group
+                          j - ng, so it waits until that group's forwards are all issued (their
+                          ev_read events exist).  One group per forward interleaves the host's
+                          geometry issue with the compute issue, so the first forward is issued
+                          right behind its geometry, not behind ng - 1 groups of it.
+    Groups are issued in group order (the order of the FPS start draws)."""
+    ngr, nunits = -(-nbat // gb), -(-nbat // u)
+    on_tail = nunits - -(-drain // u) if n_tails else 0
+    units, issued = [], 0
+    for k in range(nunits):
+        b0 = k * u
+        g, h = divmod(b0, gb)
+        before = range(issued, max(issued, g + 1))
+        limit = (g if (b0 + u) % gb == 0 else g - 1) + ng
+        after = range(before.stop, before.stop + (before.stop <= min(limit, ngr - 1)))
+        issued = after.stop
+        units.append(_Unit(g, h, g % ng, tuple(range(b0, min(b0 + u, nbat))), k % n_compute,
+                           k % n_tails if k < on_tail else None,
+                           tuple((j, j % n_geo) for j in before),
+                           tuple((j, j % n_geo) for j in after)))
+    return units
 
 
 def _batched_like(x, n):
@@ -531,9 +583,8 @@ class GraphedPipeline(PipelinedForward):
                              "geometry_batches and at least two groups")
         if geometry_cus > 0:
             geometry_streams = 1  # the CU-partitioned geometry stream is one
-        # 2 at most: with the compute and tail streams that is the 4 hardware queues a process
-        # gets (GPU_MAX_HW_QUEUES); a fifth stream shares a queue and serialises behind another
-        # (measured: 3 geometry streams 42.8k clouds/s at SSG vs 76.1k with 2)
+        # 1 to 4 geometry streams, whatever the process's hardware queues (GPU_MAX_HW_QUEUES):
+        # past them streams share queues, and the heads leave the tail streams (head_on_tail)
         if geometry_streams not in (1, 2, 3, 4):
             raise ValueError("pn2.pipeline: geometry_streams is 1 to 4")
         if compute_streams is None:
@@ -548,8 +599,8 @@ class GraphedPipeline(PipelinedForward):
         # of its own
         ts = int(tuning.get("tail_streams")) if tail_streams is None else int(tail_streams)
         self.tail_streams = 2 if ts == 2 and geometry_cus <= 0 else 1
-        self.head_on_tail = (geometry_streams + self.compute_streams + self.tail_streams <= _hw_queues() and
-                             not tuning.get("heads_on_compute"))  # A/B
+        self.head_on_tail = (geometry_streams + self.compute_streams + self.tail_streams
+                             <= _hw_queues())
         self.nslots = int(nslots)
         self.gb = gb
         self.ngroups = self.nslots // gb
@@ -559,6 +610,9 @@ class GraphedPipeline(PipelinedForward):
         self._params = None  # graphs.ParamState of the model
         self._pkey = None  # its key at the last capture
         self._slots = None  # the group slots
+        self._draws = None  # (B, N) of every FPS start draw of one batch, in layer order
+        # the start draws' pinned host buffers (_draw_all): two alternate across calls
+        self._pinned, self._pinned_evs, self._pinned_cur = [None, None], [None, None], 0
 
     def _split_index(self):
         """The SA module after which a slot's compute graph ends and its tail graph begins.  The
@@ -567,14 +621,13 @@ class GraphedPipeline(PipelinedForward):
         it, so the group_all layer runs with the head on the tail stream -- beside the next
         batch's wide sa1/sa2 kernels instead of after them.  Only with shared CUs: with
         geometry_cus > 0 the tail stream is masked to the geometry CUs, where a group_all MLP
-        would compete with FPS on a few CUs.  Tuning pipe_split_last = 1 keeps the old split (A/B).
+        would compete with FPS on a few CUs.
 
         The head graph then reads the split layer's outputs -- sa2's centroids are a static
         output of the group's fps graph -- so the group's next fps replay waits for the head
         (``ev_read`` in ``run``), not only for the sa graph."""
         k = len(self.sas) - 1
-        if (k > 0 and getattr(self.sas[k], "group_all", False) and self.geometry_cus <= 0 and
-                not tuning.get("pipe_split_last")):
+        if k > 0 and getattr(self.sas[k], "group_all", False) and self.geometry_cus <= 0:
             k -= 1
         return k
 
@@ -765,11 +818,10 @@ class GraphedPipeline(PipelinedForward):
             return outs
         gb, ng = self.gb, self.ngroups
         nbat = len(batches) - first
-        ngr = (nbat + gb - 1) // gb  # groups this call
-        geo, main, tail = _streams(dev.index, self.geometry_cus)
-        geos = [geo] + _extra_geometry_streams(dev.index, self.geometry_streams - 1)
-        mains = [main] + _extra_compute_streams(dev.index, self.compute_streams - 1)
-        tails = [tail] + ([_extra[dev.index][2]] if self.tail_streams == 2 else [])
+        ss = _stream_set(dev.index, self.geometry_cus, self.geometry_streams)
+        geos, mains = ss.geo[:self.geometry_streams], ss.compute[:self.compute_streams]
+        tails = ss.tails[:self.tail_streams]
+        geo, tail = geos[0], tails[0]
         caller = torch.cuda.current_stream(dev)
         ev0 = caller.record_event()  # one event for every pipeline stream to wait on
         for st in geos + mains + tails:
@@ -778,8 +830,10 @@ class GraphedPipeline(PipelinedForward):
         # batches no longer read its inputs / geometry (one per batch: with two compute
         # streams they finish on different streams)
         ev_fps, ev_read = [None] * ng, [[] for _ in range(ng)]
-        ev_head = [None] * (ng * gb)  # per batch slot
-        starts = self._draw_all(ngr)
+        for grp in self._slots:
+            for sl in grp.halves:
+                sl.ev_head = None
+        starts = self._draw_all((nbat + gb - 1) // gb)  # one row per group of this call
 
         tr = self.trace  # optional list of per-batch timing events (tools/debug/gpipe_events.py)
 
@@ -791,10 +845,9 @@ class GraphedPipeline(PipelinedForward):
                 e.record(stream)
                 tr[j][name] = (e, time.perf_counter())
 
-        def issue_fps(g):
+        def issue_fps(g, geo):
             s = g % ng
             grp = self._slots[s]
-            geo = geos[g % len(geos)]
             js = [first + g * gb + h for h in range(gb)]
             nh = sum(1 for j in js if j < len(batches))
             with torch.cuda.stream(geo):
@@ -813,49 +866,20 @@ class GraphedPipeline(PipelinedForward):
                 ev_fps[s] = geo.record_event()
                 mark(js[0] - first, "geo1", geo)
 
-        drain = int(tuning.get("drain_heads"))  # see the head stream choice below
-        issued = [0]  # geometry groups issued so far (always in group order: the draw order)
-
-        def top_up(force, limit):
-            # every group <= force now (a batch's own group), then at most one more while it
-            # stays <= limit: group j takes the slot of group j - ng, so it waits until that
-            # group's batches are all issued (their ev_read events exist).  One group per batch
-            # interleaves the host's geometry issue with the compute issue, so the first batch's
-            # sa graph is issued right behind its geometry, not behind ng-1 groups of it
-            while issued[0] <= min(force, ngr - 1):
-                issue_fps(issued[0])
-                issued[0] += 1
-            if issued[0] <= min(limit, ngr - 1):
-                issue_fps(issued[0])
-                issued[0] += 1
-
-        if self._slots[0].halves[0].fused:
-            try:
-                with torch.no_grad():
-                    self._run_fused(batches, extra_of, post, first, outs, ngr, geos, mains, tails,
-                                    tail, ev_fps, ev_read, ev_head, top_up, check_params, dev, mark)
-            except _Restart:
-                torch.cuda.synchronize(dev)
-                shard.set_rng_state(rng0)
-                self._slots = None
-                return self.run(batches, extras, post)
-            for g in geos[1:]:
-                geo.wait_stream(g)
-            self._pinned_evs[self._pinned_cur] = geo.record_event()  # uploads read it
-            for st in [geo] + mains + tails:
-                caller.wait_stream(st)
-            return outs
+        # one forward per geometry group (its slot is fused: u = gb batches) or per batch; the
+        # geometry runs up to ng-1 groups ahead of the compute streams (_schedule)
+        u = gb if self._slots[0].halves[0].fused else 1
+        units = _schedule(nbat, gb, ng, u, len(geos), len(mains),
+                          len(tails) if self.tail and self.head_on_tail else 0,
+                          int(tuning.get("drain_heads")))
         with torch.no_grad():
-            # the geometry runs up to ng-1 groups ahead of the compute streams
-            for i in range(first, len(batches)):
-                g, h = divmod(i - first, gb)
-                s = g % ng
-                bs = s * gb + h
-                top_up(g, -1)
-                if check_params:  # (first batch: its group's geometry is issued)
+            for un in units:
+                for g, q in un.fps_before:
+                    issue_fps(g, geos[q])
+                js = [first + b for b in un.batches]
+                if check_params:  # (first unit: its group's geometry is issued)
                     check_params = False
-                    pk = self._params.key()
-                    if pk != self._pkey:
+                    if self._params.key() != self._pkey:
                         if [id(m) for m in self._find_sas()] != [id(m) for m in self.sas]:
                             # an SA module was replaced: the geometry graphs are stale too.
                             # Take back the issued group's draws and start over (full capture)
@@ -863,41 +887,42 @@ class GraphedPipeline(PipelinedForward):
                             shard.set_rng_state(rng0)
                             self._slots = None
                             return self.run(batches, extras, post)
-                        self._recapture_forwards(extra_of(i), dev)
+                        self._recapture_forwards(extra_of(js[0]), dev)
                         self._pkey = self._params.key()
-                sl = self._slots[s].halves[h]
-                main = mains[(i - first) % len(mains)]
+                s, B = un.slot, self._slots[un.slot].B
+                sl = self._slots[s].halves[un.place]
+                main = mains[un.compute]
                 with torch.cuda.stream(main):
                     main.wait_event(ev_fps[s])
-                    if ev_head[bs] is not None:  # the batch slot's last head is done with the pool
-                        main.wait_event(ev_head[bs])
-                    for d, e in zip(sl.extra, extra_of(i)):
-                        d.copy_(e, non_blocking=True)
-                    mark(i - first, "sa0", main)
+                    if sl.ev_head is not None:  # the slot's last head is done with the pool
+                        main.wait_event(sl.ev_head)
+                    # a short last fused unit repeats its first batch in the empty places
+                    for h in range(u):
+                        for d, e in zip(sl.extra, extra_of(js[h] if h < len(js) else js[0])):
+                            (d[h * B:(h + 1) * B] if sl.fused else d).copy_(e, non_blocking=True)
+                    mark(un.batches[0], "sa0", main)
                     sl.sa.replay()
                     ev_sa = main.record_event()
-                    mark(i - first, "sa1", main)
-                # the last `drain` batches run their heads on their own (by then idle)
-                # compute streams: the tail stream runs ~2 heads behind the sa graphs, and at
-                # the end of a run that backlog is the drain
-                # consecutive batches' heads alternate between the tail streams
-                ts = tails[(i - first) % len(tails)] if (sl.head is not None and self.head_on_tail and
-                                                         i < len(batches) - drain) else main
+                    mark(un.batches[0], "sa1", main)
+                # consecutive units' heads alternate between the tail streams
+                ts = main if un.tail is None else tails[un.tail]
                 with torch.cuda.stream(ts):
                     if sl.head is not None:
                         if ts is not main:
                             ts.wait_event(ev_sa)
-                        mark(i - first, "hd0", ts)
+                        mark(un.batches[0], "hd0", ts)
                         sl.head.replay()
-                    out = _clone(sl.out)
+                    full = _clone(sl.out)
                     # recorded before `post` (e.g. an all_gather) so the group's next fps
                     # replay does not wait for the collective; a later batch of the group
                     # replaces it (same streams, later in their order)
                     ev_read[s].append(ts.record_event() if sl.tail_reads_geometry else ev_sa)
+                    res = ([_rows(full, h * B, (h + 1) * B) for h in range(len(js))]
+                           if sl.fused else [full])
                     if post is not None and ts is tail:
-                        out = post(i, out)
-                    ev_head[bs] = ts.record_event()
-                    mark(i - first, "hd1", ts)
+                        res = [post(j, o) for j, o in zip(js, res)]
+                    sl.ev_head = ts.record_event()
+                    mark(un.batches[0], "hd1", ts)
                 if post is not None and ts is not tail:
                     # heads on a compute stream or on the second tail stream: `post` (e.g. the
                     # logits' all_gather, or BatchedGather's stack of earlier batches' outputs)
@@ -906,76 +931,18 @@ class GraphedPipeline(PipelinedForward):
                     # complete on the stream that reads them
                     tail.wait_stream(ts)
                     with torch.cuda.stream(tail):
-                        for t in _flat_tensors(out):
+                        for t in _flat_tensors(full):
                             t.record_stream(tail)
-                        out = post(i, out)
-                outs.append(out)
-                top_up(-1, (g if h == gb - 1 else g - 1) + ng)
+                        res = [post(j, o) for j, o in zip(js, res)]
+                outs.extend(res)
+                for g, q in un.fps_after:
+                    issue_fps(g, geos[q])
         for g in geos[1:]:
             geo.wait_stream(g)
         self._pinned_evs[self._pinned_cur] = geo.record_event()  # uploads read it
         for st in [geo] + mains + tails:
             caller.wait_stream(st)
         return outs
-
-    def _run_fused(self, batches, extra_of, post, first, outs, ngr, geos, mains, tails, tail,
-                   ev_fps, ev_read, ev_head, top_up, check_params, dev, mark):
-        """run()'s issue loop with fused group forwards: per geometry group one sa graph (on
-        the compute streams in turn) and one head graph (tail stream) over its gb batches; the
-        outputs are split into per-batch rows, `post` runs per batch in batch order."""
-        gb, ng = self.gb, self.ngroups
-        drain = int(tuning.get("drain_heads"))
-        drain_groups = (drain + gb - 1) // gb
-        for g in range(ngr):
-            s = g % ng
-            i0 = first + g * gb
-            js = [i0 + h for h in range(gb) if i0 + h < len(batches)]
-            top_up(g, -1)
-            if check_params:  # (first group: its geometry is issued)
-                check_params = False
-                if self._params.key() != self._pkey:
-                    if [id(m) for m in self._find_sas()] != [id(m) for m in self.sas]:
-                        raise _Restart()
-                    self._recapture_forwards(extra_of(i0), dev)
-                    self._pkey = self._params.key()
-            grp = self._slots[s]
-            sl = grp.halves[0]
-            B = grp.B
-            main = mains[g % len(mains)]
-            with torch.cuda.stream(main):
-                main.wait_event(ev_fps[s])
-                if ev_head[s] is not None:  # the slot's last head is done with the pool
-                    main.wait_event(ev_head[s])
-                for h in range(gb):
-                    for d, e in zip(sl.extra, extra_of(js[h] if h < len(js) else js[0])):
-                        d[h * B:(h + 1) * B].copy_(e, non_blocking=True)
-                mark(i0 - first, "sa0", main)
-                sl.sa.replay()
-                ev_sa = main.record_event()
-                mark(i0 - first, "sa1", main)
-            ts = tails[g % len(tails)] if (sl.head is not None and self.head_on_tail and
-                                           g < ngr - drain_groups) else main
-            with torch.cuda.stream(ts):
-                if sl.head is not None:
-                    if ts is not main:
-                        ts.wait_event(ev_sa)
-                    mark(i0 - first, "hd0", ts)
-                    sl.head.replay()
-                full = _clone(sl.out)
-                ev_read[s].append(ts.record_event() if sl.tail_reads_geometry else ev_sa)
-                outs_g = [_rows(full, h * B, (h + 1) * B) for h in range(len(js))]
-                if post is not None and ts is tail:
-                    outs_g = [post(j, o) for j, o in zip(js, outs_g)]
-                ev_head[s] = ts.record_event()
-                mark(i0 - first, "hd1", ts)
-            if post is not None and ts is not tail:
-                tail.wait_stream(ts)
-                with torch.cuda.stream(tail):
-                    for t in _flat_tensors(full):
-                        t.record_stream(tail)
-                    outs_g = [post(j, o) for j, o in zip(js, outs_g)]
-            outs.extend(outs_g)
-            top_up(-1, g + ng)
 
     def _draw_all(self, k):
         """The pinned host buffer that receives the start draws of the next k groups, one row
@@ -986,8 +953,6 @@ class GraphedPipeline(PipelinedForward):
         buffers alternate across calls; one is reused once the uploads of the call before last
         ran."""
         width = self.gb * sum(B for B, _ in self._draws)
-        if not hasattr(self, "_pinned"):
-            self._pinned, self._pinned_evs, self._pinned_cur = [None, None], [None, None], 0
         c = self._pinned_cur = 1 - self._pinned_cur
         if self._pinned_evs[c] is not None:
             self._pinned_evs[c].synchronize()

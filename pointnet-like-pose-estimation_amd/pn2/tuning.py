@@ -10,9 +10,6 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
 ``dense_minwg``, ``dense_wide_minwg``, ``dense_lds``, ``dense_lds_stages``, ``dense_lds_xcd2d``,
 ``dense_lds_tile``; csrc/pn2_internal.h documents each) and these host-side ones:
 
-    tail_prio        1: the pipeline's tail stream at high priority
-    heads_on_compute 1: the pipeline's heads on the compute streams, no tail stream
-    pipe_split_last  1: the pipeline's compute/tail split after the last SA layer
     drain_heads      how many final batches of a pipelined run take their heads on their own
                      compute streams (default 2)
     geometry_stream  1: the eager forward runs layer i+1's FPS + ball query on a side stream
@@ -46,9 +43,6 @@ import os
 
 HOST_DEFAULTS = {
     "pipe_profile": 1,
-    "tail_prio": 0,
-    "heads_on_compute": 0,
-    "pipe_split_last": 0,
     "drain_heads": 2,
     "geometry_stream": 0,
     "fc_tail": 1,

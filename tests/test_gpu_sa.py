@@ -441,6 +441,50 @@ def test_graphed_pipeline_delayed_tail_matches_eager(compute_streams, geometry_s
         np.testing.assert_array_equal(g, w, err_msg="l3f of batch %d" % i)
 
 
+@pytest.mark.parametrize("geometry_streams,compute_streams", [(1, 1), (4, 2)])
+def test_graphed_pipeline_per_batch_post_keeps_batch_order(geometry_streams, compute_streams):
+    """The bench's headline issue path: one forward per batch, one batch per geometry group, two
+    tail streams and a `post` hook, 11 batches over 4 group slots (every slot reused at least
+    twice).  With 4 hardware queues, (1, 1) puts consecutive heads on alternating tail streams
+    and (4, 2) on their compute streams; either way `post` runs in batch order on one stream
+    (the order every rank's collectives must keep), the l3 features are the eager bits and the
+    CPU generator ends where the eager sequence leaves it."""
+    from pn2 import heads as H
+    from pn2 import pipeline
+    torch.manual_seed(8)
+    model = H.ClsSSG().eval()
+    cases.randomize_bn(model, 8)
+    model = model.to(DEV)
+    B, N = 8, 1024
+    xs = [cases.cloud("uniform3", B, N, 400 + i).permute(0, 2, 1).contiguous().to(DEV)
+          for i in range(11)]
+    torch.manual_seed(19)
+    with torch.no_grad():
+        want = [model(x)[1].cpu().numpy() for x in xs]
+    rng_want = torch.randint(0, 1 << 30, (4,))
+    seen = []
+
+    def post(i, o):
+        seen.append((i, torch.cuda.current_stream()))
+        torch.cuda._sleep(1_000_000)
+        return o
+
+    gp = pipeline.GraphedPipeline(model, geometry_batches=1, fuse=False, nslots=4,
+                                  geometry_bq=False, tail_streams=2,
+                                  geometry_streams=geometry_streams,
+                                  compute_streams=compute_streams)
+    assert gp.tail_streams == 2
+    assert gp.head_on_tail == (geometry_streams + compute_streams + 2 <= pipeline._hw_queues())
+    torch.manual_seed(19)
+    got = [o[1].cpu().numpy() for o in gp.run(xs, post=post)]
+    np.testing.assert_array_equal(torch.randint(0, 1 << 30, (4,)).numpy(), rng_want.numpy())
+    assert not gp._slots[0].halves[0].fused and len(gp._slots) == 4
+    assert [i for i, _ in seen] == list(range(11))
+    assert all(st == seen[0][1] for _, st in seen)
+    for i, (g, w) in enumerate(zip(got, want)):
+        np.testing.assert_array_equal(g, w, err_msg="l3f of batch %d" % i)
+
+
 def test_eval_with_autograd_is_differentiable():
     """model.eval() without torch.no_grad() (mutilthreading/predict_test.py:44-63) is
     differentiable, as the reference's eval forward is: the torch device formulation, within the

@@ -279,3 +279,74 @@ def shard_ranges(B, world):
     sys.path.insert(0, PKG)
     from pn2 import shard
     return [shard.shard_range(B, r, world) for r in range(world)]
+
+
+# GraphedPipeline's issue order, written out by hand from the two loops it replaced (one forward
+# per batch, one per fused group).  Per unit: group, place, slot, batches, compute stream, tail
+# stream (None: the head runs on the unit's compute stream), (group, geometry stream) issued
+# before and after the unit, and the limit the group issued after it must respect.
+SCHEDULES = {
+    # headline shape: one batch per group and per forward, 4 group slots, 4 geometry streams,
+    # heads alternating between 2 tail streams but for the last 2 (drain)
+    "per_batch_gb1": (dict(nbat=11, gb=1, ng=4, u=1, n_geo=4, n_compute=2, n_tails=2, drain=2), [
+        (0, 0, 0, (0,), 0, 0, ((0, 0),), ((1, 1),), 4),
+        (1, 0, 1, (1,), 1, 1, (), ((2, 2),), 5),
+        (2, 0, 2, (2,), 0, 0, (), ((3, 3),), 6),
+        (3, 0, 3, (3,), 1, 1, (), ((4, 0),), 7),
+        (4, 0, 0, (4,), 0, 0, (), ((5, 1),), 8),
+        (5, 0, 1, (5,), 1, 1, (), ((6, 2),), 9),
+        (6, 0, 2, (6,), 0, 0, (), ((7, 3),), 10),
+        (7, 0, 3, (7,), 1, 1, (), ((8, 0),), 11),
+        (8, 0, 0, (8,), 0, 0, (), ((9, 1),), 12),
+        (9, 0, 1, (9,), 1, None, (), ((10, 2),), 13),
+        (10, 0, 2, (10,), 0, None, (), (), 14)]),
+    # two batches per group, one forward per batch: a group's second batch ends it (limit g + ng),
+    # its first does not (g - 1 + ng); the last group is short
+    "per_batch_gb2": (dict(nbat=5, gb=2, ng=2, u=1, n_geo=1, n_compute=2, n_tails=1, drain=2), [
+        (0, 0, 0, (0,), 0, 0, ((0, 0),), ((1, 0),), 1),
+        (0, 1, 0, (1,), 1, 0, (), ((2, 0),), 2),
+        (1, 0, 1, (2,), 0, 0, (), (), 2),
+        (1, 1, 1, (3,), 1, None, (), (), 3),
+        (2, 0, 0, (4,), 0, None, (), (), 3)]),
+    # fused groups of 4: a short last unit of 2 batches, ceil(2 / 4) = 1 drained unit
+    "fused_gb4": (dict(nbat=18, gb=4, ng=4, u=4, n_geo=1, n_compute=2, n_tails=2, drain=2), [
+        (0, 0, 0, (0, 1, 2, 3), 0, 0, ((0, 0),), ((1, 0),), 4),
+        (1, 0, 1, (4, 5, 6, 7), 1, 1, (), ((2, 0),), 5),
+        (2, 0, 2, (8, 9, 10, 11), 0, 0, (), ((3, 0),), 6),
+        (3, 0, 3, (12, 13, 14, 15), 1, 1, (), ((4, 0),), 7),
+        (4, 0, 0, (16, 17), 0, None, (), (), 8)]),
+    "one_batch": (dict(nbat=1, gb=1, ng=4, u=1, n_geo=4, n_compute=2, n_tails=2, drain=2), [
+        (0, 0, 0, (0,), 0, None, ((0, 0),), (), 4)]),
+    "one_batch_fused": (dict(nbat=1, gb=4, ng=4, u=4, n_geo=1, n_compute=2, n_tails=2, drain=2), [
+        (0, 0, 0, (0,), 0, None, ((0, 0),), (), 4)]),
+    # no head graph / no hardware queue for a tail stream: every head on its compute stream
+    "no_tail": (dict(nbat=3, gb=1, ng=2, u=1, n_geo=2, n_compute=1, n_tails=0, drain=2), [
+        (0, 0, 0, (0,), 0, None, ((0, 0),), ((1, 1),), 2),
+        (1, 0, 1, (1,), 0, None, (), ((2, 0),), 3),
+        (2, 0, 0, (2,), 0, None, (), (), 4)]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SCHEDULES))
+def test_pipeline_schedule(name):
+    """pn2.pipeline._schedule, the index arithmetic of GraphedPipeline.run's one issue loop,
+    yields the rows above; every geometry group is issued once, in group order, by the limit of
+    the unit it follows, and group j (which takes the slot of group j - ng) only after every
+    unit of group j - ng."""
+    sys.path.insert(0, PKG)
+    from pn2.pipeline import _schedule
+    kw, want = SCHEDULES[name]
+    got = _schedule(**kw)
+    assert [tuple(un) for un in got] == [row[:8] for row in want]
+    ngr = -(-kw["nbat"] // kw["gb"])
+    issued = []  # (group, units issued before it)
+    for k, (un, row) in enumerate(zip(got, want)):
+        issued += [(g, k) for g, _ in un.fps_before]
+        assert un.group in [g for g, _ in issued]  # a unit's own geometry precedes it
+        assert len(un.fps_after) <= 1 and all(g <= row[8] for g, _ in un.fps_after)
+        if not un.fps_after:  # nothing left, or the next group is past the limit
+            assert len(issued) == ngr or len(issued) > row[8]
+        issued += [(g, k + 1) for g, _ in un.fps_after]
+    assert [g for g, _ in issued] == list(range(ngr))
+    for g, nunits in issued:
+        assert all(un.group != g - kw["ng"] for un in got[nunits:])

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import cases  # noqa: E402
 from pn2 import heads as H, geometry  # noqa: E402
-from pn2.pipeline import GraphedPipeline, _streams  # noqa: E402
+from pn2.pipeline import GraphedPipeline, partition  # noqa: E402
 
 GEO = int(os.environ.get("GEO", "32"))
 DEV = torch.device("cuda", 0)
@@ -24,7 +24,7 @@ x = cases.cloud("uniform3", 32, 1024, 90).permute(0, 2, 1).contiguous().to(DEV)
 gp = GraphedPipeline(model, geometry_cus=GEO, tail=False)
 gp.run([x] * 3)
 sl = gp._slots[0]
-geo, main, tail = _streams(0, GEO)
+geo, main = partition(0, GEO)
 
 
 def timeit(stream, fn, n=10):
