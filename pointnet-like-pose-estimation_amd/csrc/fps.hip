@@ -401,11 +401,6 @@ extern "C" int pn2_debug_fps_stamps(unsigned long long *out) {
 #endif
 
 // ------------------------------------------------------------------------- FPS side jobs
-bool &pn2::fps_side_taken() {
-    static thread_local bool taken = false;
-    return taken;
-}
-
 int pn2::fps_side_check(const pn2_fps_side &f) {
     PN2_REQUIRE(f.start_host, "pn2_fps_side: null start_host");
     const int rc = fps_check(f.pts, f.start_host, f.out_idx, f.B, f.N, f.C, f.S, nullptr, 0);

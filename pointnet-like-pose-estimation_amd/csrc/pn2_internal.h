@@ -91,30 +91,64 @@ hipError_t take_errors(unsigned *slot, int clear, unsigned *bits, hipStream_t st
 constexpr int kMaxC = 16;      // point dims (xyz + one-hot) of the register-resident kernels
 constexpr int kMaxCWide = 64;  // point dims of the streamed FPS / wide ball query (16 < C <= 64)
 
-// np: bf16 planes per operand -- 3 = fp32-accurate split products, 1 = plain bf16 products
-// sa_chain.hip: 1 launched, 0 not eligible, <0 error
-int try_launch_chain(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int pool,
-                     float *out, int64_t ostride, int64_t M, int64_t K, int np, float *ws,
-                     int64_t ws_bytes, hipStream_t st);
-// planes per operand of this thread's last chain launch (3 split bf16, 2 split fp16, 1 bf16)
-int chain_last_planes();
-// sa_dense.hip: split-bf16 layer-by-layer path for group_all / dense-row chains
-int64_t dense_split_width(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int np);
-int64_t dense_split_ws_bytes(int64_t M, int64_t w);
-// FPS side jobs of SA MLP calls (pn2_fps_side, csrc/fps.hip): argument check, the separate
-// launch (when no chain launch took the job), and the calling thread's "taken" flag that
-// try_launch_chain sets when its launch runs the job
+// ------------------------------------------------------------- SA MLP dispatch (sa_entry.cpp)
+// One call of pn2_sa_mlp_max_f32 / _bf16 as every kernel family sees it.  Each family has a pure
+// planner over (s, layers, nlayers, pool, M, K, np, T) -- no workspace pointer, no launch --
+// that the size query and the launch both run; the launch then fits the plan to (ws, ws_bytes).
+struct MlpCall {
+    const pn2_sa_src &s;
+    const pn2_mlp_layer *layers;
+    int nlayers, pool;
+    int64_t M, K;      // rows, rows per group
+    int np;            // bf16 planes per operand: 3 = fp32-accurate split products, 1 = plain bf16
+    const char *name;  // the entry point, for error texts
+    Tuning T;          // the call's one snapshot
+    float *out;
+    int64_t ostride;
+    float *ws;
+    int64_t ws_bytes;
+    hipStream_t st;
+};
+// what a call ran (pn2_sa_mlp_last_path / _planes / _fps_side): filled by the family that
+// launched, kept by the entry point when the whole call succeeded
+struct MlpReport {
+    int path = 0;       // PN2_PATH_*
+    int planes = 0;     // planes per operand carrying most of the flops (0: fp32 kernels)
+    int fps_side = -1;  // -1 no job, 1 inside the chain launch, 0 a launch of its own
+};
+// 1: launched (r filled), 0: not eligible, <0: error -- tried in this order
+int try_launch_chain(const MlpCall &c, MlpReport &r);  // sa_chain.hip
+int try_launch_dense(const MlpCall &c, MlpReport &r);  // sa_dense.hip: layer by layer
+int try_launch_f32(const MlpCall &c, MlpReport &r);    // sa_mlp.hip: fp32 MFMA segments (np == 3)
+// workspace bytes the family's plan for this call asks for (0: none, or not eligible)
+int64_t chain_ws_bytes(const MlpCall &c);
+int64_t dense_ws_bytes(const MlpCall &c);
+int64_t f32_ws_bytes(const MlpCall &c);
+// FPS side jobs of SA MLP calls (pn2_fps_side, csrc/fps.hip): argument check, and the separate
+// launch when no chain launch took the job
 int fps_side_check(const pn2_fps_side &f);
 int fps_side_launch(const pn2_fps_side &f, hipStream_t st);
-bool &fps_side_taken();
-// planes per operand carrying most of the flops of the calling thread's last dense-layer call
-int dense_last_planes();
-int try_launch_dense_split(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int pool,
-                           float *out, int64_t ostride, float *ws, int64_t ws_bytes, int64_t M,
-                           int64_t K, int np, hipStream_t st);
-int launch_layer0_prepass(const pn2_sa_src &s, const pn2_mlp_layer &L0, float *z, hipStream_t st);
-// bytes of workspace the chain kernel's layer-0 pre-pass needs for this chain (0: not used)
-int64_t chain_prepass_bytes(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int np);
+// the chain's layer-0 pre-pass (sa_dense.hip)
+int launch_layer0_prepass(const pn2_sa_src &s, const pn2_mlp_layer &L0, float *z, const Tuning &T,
+                          hipStream_t st);
+
+// whether rows of D floats at p (row / batch strides in floats) can be read as 16-byte pieces;
+// empty_ok: what a source without such rows (D == 0) answers
+static inline bool rows_16b(const float *p, int64_t D, int64_t rstride, int64_t bstride, bool empty_ok) {
+    if (D == 0) return empty_ok;
+    return D > 0 && D % 4 == 0 && ((uintptr_t)p & 15) == 0 && rstride % 4 == 0 && bstride % 4 == 0;
+}
+static inline bool ws_fits(const void *ws, int64_t ws_bytes, int64_t need) {
+    return ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= need;
+}
+// zero a pooled output [G][cols] (row stride ostride) that its kernel merges into by atomicMax
+static inline int zero_pooled_output(float *out, int64_t ostride, int64_t G, int64_t cols, hipStream_t st,
+                                     const char *what) {
+    const hipError_t e = ostride == cols
+                             ? hipMemsetAsync(out, 0, (size_t)G * cols * 4, st)
+                             : hipMemset2DAsync(out, (size_t)ostride * 4, 0, (size_t)cols * 4, (size_t)G, st);
+    return e == hipSuccess ? PN2_OK : set_error(PN2_EHIP, "%s: memset: %s", what, hipGetErrorString(e));
+}
 
 // --------------------------------------------------------------- device: reference sum orders
 // torch.sum(x**2, -1) over the channel axis, reproduced bit-for-bit (torch 2.10 CPU, AVX512);

@@ -1194,8 +1194,6 @@ static int launch_chain_sig(const ChainArgs &A, unsigned grid, size_t lds, hipSt
     }
 }
 
-// planes of the last chain launch on this thread (pn2_sa_mlp_last_planes)
-static thread_local int g_last_planes = 0;
 
 // the compiled KB0M for this chain: the smallest resident bound >= kb0, else 0 (streamed);
 // -1 when (T0, T1) has no instance
@@ -1208,41 +1206,28 @@ static int chain_kb0m(int T0, int T1, int kb0) {
     return best;
 }
 
-// Layer-0 pre-pass (KB0M = -1).  Layer 0 is linear in [xyz - centroid | features], so
-// W0 . row = W0 . [xyz | features](point) - W0_xyz . centroid: the first term depends only on
-// the source point and is computed once per point (launch_layer0_prepass) instead of once per
-// (group, neighbour) row -- K*S/N times fewer products (16x at SSG sa2) -- and the chain gathers
-// it in place of the raw row.  Used for wide first layers (>= 5 k-blocks) of fp32 chains with
-// a compiled (T0, T1, -1) instance when the rows outnumber the points 4:1, given workspace.
-static bool chain_use_prepass(const pn2_sa_src &s, const pn2_mlp_layer *layers, int T0, int T1,
-                              int kb0, int64_t M, int np) {
-    if (np != 3 || kb0 < 5 || s.C < 1 || s.C > kMaxC || !layers[0].wt) return false;
-    if (!tuning().chain_prepass) return false;
-    if (4 * s.B * s.N > M) return false;
-    bool has = false;
-#define PN2_CHAIN_HAS(a, b, c) \
-    if (c < 0 && T0 == a && T1 == b) has = true;
-    PN2_CHAIN_SIGS(PN2_CHAIN_HAS)
-#undef PN2_CHAIN_HAS
-    return has;
-}
+constexpr int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
 
-static bool chain_shape(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int pool,
-                        int &T0, int &T1, int (&kbs)[3]) {
-    if (nlayers != 3 || !pool) return false;
-    if (s.mode != PN2_SRC_GROUP_XYZ_FIRST && s.mode != PN2_SRC_GROUP_FEAT_FIRST) return false;
-    if (s.C > kMaxC) return false;
-    for (int l = 0; l < 3; ++l)
-        if (!layers[l].wt_split || ((uintptr_t)layers[l].wt_split & 15) ||
-            (layers[l].flags & PN2_LAYER_NO_RELU))
-            return false;
-    T0 = (int)(layers[0].cout / 32);
-    T1 = (int)(layers[1].cout / 32);
-    kbs[0] = (int)pn2_layer_split_kblocks(layers[0].cin, s.C);
-    kbs[1] = (int)((layers[1].cin + 15) / 16);
-    kbs[2] = (int)((layers[2].cin + 15) / 16);
-    return kbs[0] >= 1;
-}
+// Everything a chain launch decides.  plan_chain fills the first part from the shapes alone;
+// chain_fit, given the caller's workspace, settles the rest.
+struct ChainPlan {
+    bool ok = false;  // eligible: a compiled (T0, T1) instance for this source and these layers
+    int T0 = 0, T1 = 0, kbs[3] = {0, 0, 0};  // column tiles of layers 0 / 1, k-blocks per layer
+    int KB0M = 0;     // the instance's layer-0 bound (0: streamed; -1 once the pre-pass is in)
+    // workspace: [pre-pass z | pre-pass u | compact unit table | descriptors]; the chain runs
+    // without a table that does not fit
+    bool want_pre = false, want_compact = false;
+    int64_t z_bytes = 0, pre_bytes = 0, compact_bytes = 0;  // z; z + u; units + descriptors
+    int64_t bytes() const { return (want_pre ? pre_bytes : 0) + (want_compact ? compact_bytes : 0); }
+    // ---- chain_fit
+    bool pre = false, compact = false;
+    int64_t compact_off = 0;  // of the unit table in the workspace
+    int npk = 0;              // planes per operand of the launch (3 split bf16, 2 split fp16, 1 bf16)
+    int pool_mode = 0, pool_rows = 0, ks = 0, wpc = 0;
+    unsigned grid = 0;
+    int lds_bn = 0, lds_ring = 0;  // LDS: [pool][BN scale/shift][per-wave rings]
+    size_t lds = 0;
+};
 
 // compact neighbourhoods (pool_mode 3): groups of K in [9, 128] (K <= 8 is one unit anyway),
 // given the ball query's counts, the scan kernel's LDS within one CU's 160 KB.  Tuning
@@ -1253,89 +1238,84 @@ static int64_t compact_wpc(const pn2_sa_src &s) {
 static size_t compact_scan_lds(const pn2_sa_src &s) {
     return (size_t)(2 * s.S + compact_wpc(s) + 32) * 4;
 }
-static bool chain_use_compact(const pn2_sa_src &s) {
-    if (!s.cnt || s.K <= kUnitRows || s.K > 128 || s.S < 1) return false;
-    if (compact_scan_lds(s) > (size_t)160 * 1024) return false;
-    if (!tuning().compact) return false;
-    return true;
-}
-static int64_t compact_table_bytes(const pn2_sa_src &s) {
-    return s.B * compact_wpc(s) * (kUnitsPerWG * 4 + 8);
-}
 
-// the pre-pass tables: z [B*N][cout0] and u [B*S][cout0], 16-byte aligned each
-static int64_t prepass_z_bytes(const pn2_sa_src &s, const pn2_mlp_layer &L0) {
-    return (s.B * s.N * L0.cout * 4 + 15) / 16 * 16;
-}
-static int64_t prepass_bytes(const pn2_sa_src &s, const pn2_mlp_layer &L0) {
-    return prepass_z_bytes(s, L0) + (s.B * s.S * L0.cout * 4 + 15) / 16 * 16;
-}
-
-// workspace of a chain launch: [pre-pass z | pre-pass u | compact unit table | descriptors]
-int64_t chain_prepass_bytes(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int np) {
-    int T0, T1, kbs[3];
-    if (!chain_shape(s, layers, nlayers, 1, T0, T1, kbs)) return 0;
-    if (chain_kb0m(T0, T1, kbs[0]) < 0) return 0;
-    const int64_t M = s.B * s.S * s.K;
-    int64_t bytes = 0;
-    if (chain_use_prepass(s, layers, T0, T1, kbs[0], M, np))
-        bytes += prepass_bytes(s, layers[0]);
-    if (chain_use_compact(s)) bytes += compact_table_bytes(s);
-    return bytes;
-}
-
-// 1: launched, 0: this chain is not eligible (caller uses the fp32 kernels), <0: error
-int try_launch_chain(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int pool,
-                     float *out, int64_t ostride, int64_t M, int64_t K, int np, float *ws,
-                     int64_t ws_bytes, hipStream_t st) {
-    if (np == 3 && tuning().mlp_f32) return 0;
+static ChainPlan plan_chain(const MlpCall &c) {
+    ChainPlan P;
+    const pn2_sa_src &s = c.s;
+    const pn2_mlp_layer *layers = c.layers;
+    if (c.np == 3 && c.T.mlp_f32) return P;
+    if (c.nlayers != 3 || !c.pool) return P;
+    if (s.mode != PN2_SRC_GROUP_XYZ_FIRST && s.mode != PN2_SRC_GROUP_FEAT_FIRST) return P;
+    if (s.C > kMaxC) return P;
+    for (int l = 0; l < 3; ++l)
+        if (!layers[l].wt_split || ((uintptr_t)layers[l].wt_split & 15) ||
+            (layers[l].flags & PN2_LAYER_NO_RELU))
+            return P;
     // k-blocks per layer (the first layer's rows are [xyz | features], see split_in_channel)
-    int T0, T1, kbs[3];
-    if (!chain_shape(s, layers, nlayers, pool, T0, T1, kbs)) return 0;
-    int KB0M = chain_kb0m(T0, T1, kbs[0]);
-    if (KB0M < 0) return 0;
+    const int T0 = P.T0 = (int)(layers[0].cout / 32), T1 = P.T1 = (int)(layers[1].cout / 32);
+    P.kbs[0] = (int)pn2_layer_split_kblocks(layers[0].cin, s.C);
+    P.kbs[1] = (int)((layers[1].cin + 15) / 16);
+    P.kbs[2] = (int)((layers[2].cin + 15) / 16);
+    if (P.kbs[0] < 1) return P;
+    P.KB0M = chain_kb0m(T0, T1, P.kbs[0]);
+    if (P.KB0M < 0) return P;
     // bf16 chains stream a multi-block layer-0 input rather than hold it resident: the
     // resident block takes the VGPRs of a wave per SIMD (STRESS sa2 (4,4): 144 -> 112 VGPRs,
     // 3 -> 4 waves/SIMD; eager 265 -> 193 us, pipelined STRESS 124.6k -> 130.1k clouds/s).  The
     // split (fp32) chains gain nothing: (4,4,9) 158, (4,4,0) 151 VGPRs, both 3 waves/SIMD.
-    if (np == 1 && KB0M > 1 && chain_kb0m(T0, T1, 1 << 20) == 0) KB0M = 0;
+    if (c.np == 1 && P.KB0M > 1 && chain_kb0m(T0, T1, 1 << 20) == 0) P.KB0M = 0;
+    P.want_compact = s.cnt && s.K > kUnitRows && s.K <= 128 && s.S >= 1 &&
+                     compact_scan_lds(s) <= (size_t)160 * 1024 && c.T.compact;
     // without compaction a 32-row slab must hold rows of one group (K = 8, 16: several whole
     // groups; K % 32 == 0: part of one)
-    if (!(pool && chain_use_compact(s)) && !(K == 8 || K == 16 || K % 32 == 0)) return 0;
-    const int64_t pbytes = prepass_bytes(s, layers[0]);
-    const bool pre = chain_use_prepass(s, layers, T0, T1, kbs[0], M, np) && ws &&
-                     ws_bytes >= pbytes && ((uintptr_t)ws & 15) == 0;
-    const int64_t zb = pre ? pbytes : 0;
-    bool compact = pool && chain_use_compact(s) && ws && ((uintptr_t)ws & 15) == 0 &&
-                   ws_bytes >= zb + compact_table_bytes(s);
-    // With the layer-0 pre-pass (wide first layers: SSG / pose sa2) compaction paid only once
-    // the centroid term u came from a global table instead of being computed
-    // per workgroup for its 16 groups (setup 8.8 us of a 49 us workgroup life,
-    // tools/debug/chain_stamps.py): SSG sa2 115 us vs 130 us computing the padding rows.
-    float *utab = pre ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + prepass_z_bytes(s, layers[0]))
-                      : nullptr;
-    if (pre) {
-        const int rc = launch_layer0_prepass(s, layers[0], ws, st);
-        if (rc != PN2_OK) return rc;
-        if (!compact) {  // with compaction the scan launch's extra workgroups compute u
-            const int64_t G = s.B * s.S, cout0 = layers[0].cout;
-            hipLaunchKernelGGL(u_table_kernel, dim3((unsigned)((G * cout0 + 255) / 256)), dim3(256), 0, st,
-                               layers[0].wt, (int)(layers[0].cin - s.C), (int)cout0, s.ctr, (int)s.C, G,
-                               utab);  // the fp32 image's rows are [features | xyz]
-            PN2_LAUNCH_CHECK("u_table_kernel");
-        }
-        KB0M = -1;
-    }
+    if (!P.want_compact && !(c.K == 8 || c.K == 16 || c.K % 32 == 0)) return P;
+    // Layer-0 pre-pass (KB0M = -1).  Layer 0 is linear in [xyz - centroid | features], so
+    // W0 . row = W0 . [xyz | features](point) - W0_xyz . centroid: the first term depends only on
+    // the source point and is computed once per point (launch_layer0_prepass) instead of once per
+    // (group, neighbour) row -- K*S/N times fewer products (16x at SSG sa2) -- and the chain gathers
+    // it in place of the raw row.  Used for wide first layers (>= 5 k-blocks) of fp32 chains with
+    // a compiled (T0, T1, -1) instance when the rows outnumber the points 4:1, given workspace.
+    bool pre_sig = false;
+#define PN2_CHAIN_HAS(a, b, c_) \
+    if (c_ < 0 && T0 == a && T1 == b) pre_sig = true;
+    PN2_CHAIN_SIGS(PN2_CHAIN_HAS)
+#undef PN2_CHAIN_HAS
+    P.want_pre = pre_sig && c.np == 3 && P.kbs[0] >= 5 && s.C >= 1 && layers[0].wt && c.T.chain_prepass &&
+                 4 * s.B * s.N <= c.M;
+    // the pre-pass tables: z [B*N][cout0] and u [B*S][cout0], 16-byte aligned each
+    P.z_bytes = align16(s.B * s.N * layers[0].cout * 4);
+    P.pre_bytes = P.z_bytes + align16(s.B * s.S * layers[0].cout * 4);
+    P.compact_bytes = s.B * compact_wpc(s) * (kUnitsPerWG * 4 + 8);
+    P.ok = true;
+    return P;
+}
+
+int64_t chain_ws_bytes(const MlpCall &c) {
+    const ChainPlan P = plan_chain(c);
+    return P.ok ? P.bytes() : 0;
+}
+
+// The plan against the caller's workspace: which tables fit, and what follows from that -- the
+// planes, the pool, the ring depth, the grid and the LDS layout.
+static void chain_fit(ChainPlan &P, const MlpCall &c) {
+    const pn2_sa_src &s = c.s;
+    const pn2_mlp_layer *layers = c.layers;
+    const int64_t K = c.K, coutL = layers[2].cout;
+    P.pre = P.want_pre && ws_fits(c.ws, c.ws_bytes, P.pre_bytes);
+    P.compact_off = P.pre ? P.pre_bytes : 0;
+    P.compact = P.want_compact && ws_fits(c.ws, c.ws_bytes, P.compact_off + P.compact_bytes);
+    if (P.pre) P.KB0M = -1;
     // the fp32-accurate chains run split fp16 (3 MFMAs per product, split_bf16.h) where a whole
     // layer-0 input is in registers or pre-transformed (the activation scale needs the wave's
     // whole input); tuning chain_f16 = 0 keeps split bf16 (6 MFMAs)
     // The activation scale is per wave (32 rows): a cloud's rows must start at a wave boundary
     // (compact launches: a workgroup per cloud; else S*K a multiple of 32), so a cloud's results
     // never depend on which other clouds share its batch.
-    const bool f16_ok = compact || (s.S * K) % 32 == 0;
-    const int npk = (np == 3 && tuning().chain_f16 && f16_ok && (KB0M == 1 || KB0M == -1)) ? 2 : np;
-    const size_t stage_b = npk == 3 ? stage_bytes<3>() : npk == 2 ? stage_bytes<2>() : stage_bytes<1>();
-    const int wpc = compact ? (int)compact_wpc(s) : 0;
+    const bool f16_ok = P.compact || (s.S * K) % 32 == 0;
+    P.npk = (c.np == 3 && c.T.chain_f16 && f16_ok && (P.KB0M == 1 || P.KB0M == -1)) ? 2 : c.np;
+    const size_t stage_b = P.npk == 3 ? stage_bytes<3>() : P.npk == 2 ? stage_bytes<2>() : stage_bytes<1>();
+    const size_t bn_bytes = (size_t)2 * 4 * (layers[0].cout + layers[1].cout + coutL);
+    P.wpc = P.compact ? (int)compact_wpc(s) : 0;
     // Compact launches: the weight ring's depth against the LDS group pool.  With the full
     // 16-row pool a 3-stage ring cost a workgroup per CU (SSG sa2: 3 -> 2 live per CU, 114 ->
     // 130 us, although each workgroup lived 36 us instead of 45: tools/debug/chain_stamps.py).
@@ -1350,36 +1330,77 @@ int try_launch_chain(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlaye
     // cap at 3 waves per SIMD; PMC write 7.9 vs 5.4 MB per call), eager sa1 49.0 -> 46.0 us, sa2
     // 82.5 -> 81.6 us; pipelined SSG K = 20 166.3-167.2k -> 170.3-172.3k, K = 100 190.6-191.1k
     // -> 190.3-194.7k, MSG / POSE / STRESS +1-2 % (tools/pmc_ab.sh, tools/args_ab.sh).
-    int cks = 2, cprow = kUnitsPerWG;
-    if (compact) {
-        const int64_t cL = layers[2].cout;
-        const size_t bnb = (size_t)2 * 4 * (layers[0].cout + layers[1].cout + cL) + 32;
-        const size_t sb = stage_b;
-        const int occ_v = T1 >= 4 ? 3 : T1 == 3 ? 4 : 5;  // workgroups per CU the VGPRs allow
+    P.ks = 2, P.pool_rows = kUnitsPerWG;
+    if (P.compact) {
+        const size_t bnb = bn_bytes + 32;
+        const int occ_v = P.T1 >= 4 ? 3 : P.T1 == 3 ? 4 : 5;  // workgroups per CU the VGPRs allow
         auto wgs = [&](int ks, int prow) {
-            return std::min<int64_t>(occ_v, (int64_t)(160 * 1024) / (int64_t)(prow * cL * 4 + bnb + ks * sb));
+            return std::min<int64_t>(occ_v, (int64_t)(160 * 1024) / (int64_t)(prow * coutL * 4 + bnb + ks * stage_b));
         };
         // an 8-row pool when it buys a workgroup per CU (SSG sa1 eager: 4 -> 5 per CU, 62.4 ->
         // 59.9 us; its many small groups past the 8th of a workgroup merge through HBM atomics)
         // -- unless tuning compact_pool sets the pool rows (default 16: in the pipeline the
         // full pool measured faster, see above)
-        if (wgs(2, 8) > wgs(2, kUnitsPerWG)) cprow = 8;
-        if (tuning().compact_pool > 0)
-            cprow = (int)std::max<int64_t>(1, std::min<int64_t>(kUnitsPerWG, tuning().compact_pool));
+        if (wgs(2, 8) > wgs(2, kUnitsPerWG)) P.pool_rows = 8;
+        if (c.T.compact_pool > 0)
+            P.pool_rows = (int)std::max<int64_t>(1, std::min<int64_t>(kUnitsPerWG, c.T.compact_pool));
         // the 3-stage ring where it keeps the workgroups per CU: with the whole pool when that
         // fits too (split-fp16 rings are a third smaller: SSG sa2 then needs no HBM merges),
         // else with the 8-row pool
-        if (tuning().compact_stages == 3) {
-            if (wgs(3, cprow) >= wgs(2, kUnitsPerWG)) cks = 3;
-            else if (wgs(3, 8) >= wgs(2, kUnitsPerWG)) cks = 3, cprow = 8;
+        if (c.T.compact_stages == 3) {
+            if (wgs(3, P.pool_rows) >= wgs(2, kUnitsPerWG)) P.ks = 3;
+            else if (wgs(3, 8) >= wgs(2, kUnitsPerWG)) P.ks = 3, P.pool_rows = 8;
+        }
+    }
+    size_t pool_lds = 0;
+    if (P.compact) {
+        P.pool_mode = 3;
+        pool_lds = (size_t)P.pool_rows * coutL * 4;
+    } else if (K == 8 || K == 16 || K == 32) {
+        P.pool_mode = 0;
+    } else if (kChainRows % K == 0) {
+        P.pool_mode = 1;
+        pool_lds = (size_t)(kChainRows / K) * coutL * 4;
+    } else {
+        P.pool_mode = 2;
+    }
+    if (pool_lds > 32 * 1024 && !P.compact) P.pool_mode = 2, pool_lds = 0;
+    P.grid = P.compact ? (unsigned)(s.B * P.wpc) : (unsigned)((c.M + kChainRows - 1) / kChainRows);
+    P.lds_bn = (int)align16((int64_t)pool_lds);
+    P.lds_ring = (int)align16(P.lds_bn + (int64_t)bn_bytes);
+    P.lds = (size_t)P.lds_ring + (size_t)(P.compact ? P.ks : kStages) * stage_b;
+}
+
+// 1: launched, 0: this chain is not eligible, <0: error
+int try_launch_chain(const MlpCall &c, MlpReport &r) {
+    ChainPlan P = plan_chain(c);
+    if (!P.ok) return 0;
+    chain_fit(P, c);
+    const pn2_sa_src &s = c.s;
+    const pn2_mlp_layer *layers = c.layers;
+    hipStream_t st = c.st;
+    char *ws = reinterpret_cast<char *>(c.ws);
+    // With the layer-0 pre-pass (wide first layers: SSG / pose sa2) compaction paid only once
+    // the centroid term u came from a global table instead of being computed
+    // per workgroup for its 16 groups (setup 8.8 us of a 49 us workgroup life,
+    // tools/debug/chain_stamps.py): SSG sa2 115 us vs 130 us computing the padding rows.
+    float *utab = P.pre ? reinterpret_cast<float *>(ws + P.z_bytes) : nullptr;
+    if (P.pre) {
+        const int rc = launch_layer0_prepass(s, layers[0], c.ws, c.T, st);
+        if (rc != PN2_OK) return rc;
+        if (!P.compact) {  // with compaction the scan launch's extra workgroups compute u
+            const int64_t G = s.B * s.S, cout0 = layers[0].cout;
+            hipLaunchKernelGGL(u_table_kernel, dim3((unsigned)((G * cout0 + 255) / 256)), dim3(256), 0, st,
+                               layers[0].wt, (int)(layers[0].cin - s.C), (int)cout0, s.ctr, (int)s.C, G,
+                               utab);  // the fp32 image's rows are [features | xyz]
+            PN2_LAUNCH_CHECK("u_table_kernel");
         }
     }
     int *cunits = nullptr;
     int2 *cdesc = nullptr;
-    if (compact) {
-        cunits = reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + zb);
-        cdesc = reinterpret_cast<int2 *>(cunits + s.B * wpc * kUnitsPerWG);
-        const size_t slds = compact_scan_lds(s);
+    if (P.compact) {
+        cunits = reinterpret_cast<int *>(ws + P.compact_off);
+        cdesc = reinterpret_cast<int2 *>(cunits + s.B * P.wpc * kUnitsPerWG);
         // u's workgroups (pre-pass chains): ~4 outputs per thread
         const int64_t ut = utab ? s.B * s.S * layers[0].cout : 0;
         const unsigned nu = (unsigned)std::min<int64_t>(std::min<int64_t>(1024, s.B * s.S),
@@ -1388,9 +1409,9 @@ int try_launch_chain(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlaye
             reinterpret_cast<const void *>(&compact_scan_kernel),
             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)attr;
-        hipLaunchKernelGGL(compact_scan_kernel, dim3((unsigned)s.B + nu), dim3(kScanThreads), slds, st,
-                           s.cnt, (int)s.B, (int)s.S, (int)s.K, wpc, cunits, cdesc, out, ostride,
-                           (int)layers[2].cout, cprow, layers[0].wt, (int)(layers[0].cin - s.C),
+        hipLaunchKernelGGL(compact_scan_kernel, dim3((unsigned)s.B + nu), dim3(kScanThreads), compact_scan_lds(s),
+                           st, s.cnt, (int)s.B, (int)s.S, (int)s.K, P.wpc, cunits, cdesc, c.out, c.ostride,
+                           (int)layers[2].cout, P.pool_rows, layers[0].wt, (int)(layers[0].cin - s.C),
                            (int)layers[0].cout, s.ctr, (int)s.C, utab);
         PN2_LAUNCH_CHECK("compact_scan_kernel");
     }
@@ -1401,81 +1422,60 @@ int try_launch_chain(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlaye
         A.L[l].w = reinterpret_cast<const bf16x8 *>(layers[l].wt_split);
         A.L[l].alpha = layers[l].alpha;
         A.L[l].beta = layers[l].beta;
-        A.L[l].kb = kbs[l];
+        A.L[l].kb = P.kbs[l];
         A.L[l].tiles = (int)(layers[l].cout / 32);
-        if (npk == 2 && !(l == 0 && pre)) {  // (a pre-transformed layer 0 runs no MFMA here)
-            A.L[l].w = split_f16_planes(layers[l].wt_split, layers[l].cout, kbs[l]);
-            A.L[l].wscale = split_f16_inv_scale(layers[l].wt_split, layers[l].cout, kbs[l]);
+        if (P.npk == 2 && !(l == 0 && P.pre)) {  // (a pre-transformed layer 0 runs no MFMA here)
+            A.L[l].w = split_f16_planes(layers[l].wt_split, layers[l].cout, P.kbs[l]);
+            A.L[l].wscale = split_f16_inv_scale(layers[l].wt_split, layers[l].cout, P.kbs[l]);
         }
     }
-    A.M = (int)M;
-    A.K = (int)K;
+    A.M = (int)c.M;
+    A.K = (int)c.K;
     A.S = (int)s.S;
     A.C = (int)s.C;
     A.D = (int)s.D;
-    A.out = out;
-    A.ostride = ostride;
-    A.vec_feat = (s.D > 0 && s.D % 4 == 0 && ((uintptr_t)s.feat & 15) == 0 && s.fn % 4 == 0 &&
-                  s.fb % 4 == 0) ? 1 : 0;
+    A.out = c.out;
+    A.ostride = c.ostride;
+    A.vec_feat = rows_16b(s.feat, s.D, s.fn, s.fb, false) ? 1 : 0;
     A.cunits = cunits;
     A.cdesc = cdesc;
-    A.wpc = wpc;
-    if (pre) {
-        A.z = ws;
+    A.wpc = P.wpc;
+    if (P.pre) {
+        A.z = c.ws;
         A.u = utab;
     }
-    const int64_t coutL = layers[2].cout;
-    size_t lds = 0;
-    if (compact) {
-        A.pool_mode = 3;
-        A.pool_rows = cprow;
-        A.ks = cks;
-        lds = (size_t)cprow * coutL * 4;
-    } else if (K == 8 || K == 16 || K == 32) {
-        A.pool_mode = 0;
-    } else if (kChainRows % K == 0) {
-        A.pool_mode = 1;
-        lds = (size_t)(kChainRows / K) * coutL * 4;
-    } else {
-        A.pool_mode = 2;
+    A.pool_mode = P.pool_mode;
+    if (P.compact) {
+        A.pool_rows = P.pool_rows;
+        A.ks = P.ks;
     }
-    if (lds > 32 * 1024 && !compact) A.pool_mode = 2, lds = 0;
-    if (A.pool_mode == 2) {
-        const int64_t G = M / K;
-        hipError_t e = (ostride == coutL)
-                           ? hipMemsetAsync(out, 0, (size_t)G * coutL * 4, st)
-                           : hipMemset2DAsync(out, (size_t)ostride * 4, 0, (size_t)coutL * 4, (size_t)G, st);
-        if (e != hipSuccess) return set_error(PN2_EHIP, "sa_chain: memset: %s", hipGetErrorString(e));
+    A.lds_bn = P.lds_bn;
+    A.lds_ring = P.lds_ring;
+    if (P.pool_mode == 2) {
+        const int rc = zero_pooled_output(c.out, c.ostride, c.M / c.K, layers[2].cout, st, "sa_chain");
+        if (rc != PN2_OK) return rc;
     }
-    const unsigned grid = compact ? (unsigned)(s.B * wpc) : (unsigned)((M + kChainRows - 1) / kChainRows);
-    // LDS: [pool][BN scale/shift][per-wave rings]
-    A.lds_bn = (int)((lds + 15) / 16 * 16);
-    const size_t bn_bytes = (size_t)2 * 4 * (layers[0].cout + layers[1].cout + coutL);
-    A.lds_ring = (int)((A.lds_bn + bn_bytes + 15) / 16 * 16);
-    lds = (size_t)A.lds_ring + (size_t)(compact ? cks : kStages) * stage_b;
     // the caller's FPS side job rides on this launch when the instance has it (KB0M == 1: the
     // xyz-only first layers, i.e. sa1) and it fits the chain's LDS
-    unsigned lgrid = grid;
-    if (s.fps_side && KB0M == 1 && tuning().fps_side && fps_side_block_args(*s.fps_side, lds, A.fps)) {
+    unsigned lgrid = P.grid;
+    if (s.fps_side && P.KB0M == 1 && c.T.fps_side && fps_side_block_args(*s.fps_side, P.lds, A.fps)) {
         A.fps_nb = (int)s.fps_side->B;
         A.fps_blocks = (A.fps_nb + 7) / 8 * 8;
         lgrid += (unsigned)A.fps_blocks;
     }
     int rc = PN2_EUNSUPPORTED;
-#define PN2_CHAIN_GO(a, b, c)                                                             \
-    if (T0 == a && T1 == b && KB0M == c)                                                  \
-        rc = npk == 3 ? launch_chain_sig<a, b, c, 3>(A, lgrid, lds, st)                   \
-           : npk == 2 ? launch_chain_sig<a, b, c, 2>(A, lgrid, lds, st)                   \
-                      : launch_chain_sig<a, b, c, 1>(A, lgrid, lds, st);
+#define PN2_CHAIN_GO(a, b, c_)                                                            \
+    if (P.T0 == a && P.T1 == b && P.KB0M == c_)                                           \
+        rc = P.npk == 3 ? launch_chain_sig<a, b, c_, 3>(A, lgrid, P.lds, st)              \
+           : P.npk == 2 ? launch_chain_sig<a, b, c_, 2>(A, lgrid, P.lds, st)              \
+                        : launch_chain_sig<a, b, c_, 1>(A, lgrid, P.lds, st);
     PN2_CHAIN_SIGS(PN2_CHAIN_GO)
 #undef PN2_CHAIN_GO
-    if (rc == PN2_OK) {
-        g_last_planes = npk;
-        if (A.fps_blocks) fps_side_taken() = true;
-    }
-    return rc == PN2_OK ? 1 : rc;
+    if (rc != PN2_OK) return rc;
+    r.path = PN2_PATH_SPLIT_BF16;
+    r.planes = P.npk;
+    if (A.fps_blocks) r.fps_side = 1;
+    return 1;
 }
 
 }  // namespace pn2
-
-int pn2::chain_last_planes() { return pn2::g_last_planes; }

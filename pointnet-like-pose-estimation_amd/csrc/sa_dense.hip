@@ -870,13 +870,13 @@ void dense_lds_kernel(const DenseSplitArgs A) {
 // 64 x 64 -- and pools (0: not eligible).  Tuning dense_lds_tile forces one.
 static const int kLdsTiles[] = {82, 44, 42, 22};
 
-static int dense_lds_tile(const DenseSplitArgs &A) {
-    if (!tuning().dense_lds || !A.vec) return 0;
-    if (tuning().dense_lds == 2 && A.mode == 0) return 0;  // 2: group_all / pre-pass layers only
+static int dense_lds_tile(const DenseSplitArgs &A, const Tuning &T) {
+    if (!T.dense_lds || !A.vec) return 0;
+    if (T.dense_lds == 2 && A.mode == 0) return 0;  // 2: group_all / pre-pass layers only
     // tuning dense_lds_mincin keeps narrower layers on the register-staged kernel (default 0:
     // none -- SSG eager 67.6k at 0 or 128 vs 66.6k at 256, PointNet-v1 equal or faster,
     // tools/gpu_r04af.sh)
-    if ((A.mode == 0 ? A.cin : A.D) < tuning().dense_lds_mincin) return 0;
+    if ((A.mode == 0 ? A.cin : A.D) < T.dense_lds_mincin) return 0;
     const bool ok = A.mode == 0 ? (A.cin % 32 == 0 && A.kb * 16 == A.cin && A.rs % 4 == 0 &&
                                    ((uintptr_t)A.rows & 15) == 0)
                                 : (A.feat && A.D > 0 && A.D % 32 == 0 && A.kb == 1 + A.D / 16 &&
@@ -886,7 +886,7 @@ static int dense_lds_tile(const DenseSplitArgs &A) {
         const int tr = 32 * (t / 10), ntw = t % 10;
         return A.tiles % ntw == 0 && (!A.pool || (A.K % 32 == 0 && (tr % A.K == 0 || A.K % tr == 0)));
     };
-    if (const int64_t f = tuning().dense_lds_tile) return fits((int)f) ? (int)f : 0;
+    if (const int64_t f = T.dense_lds_tile) return fits((int)f) ? (int)f : 0;
     for (int t : kLdsTiles) {
         const int tr = 32 * (t / 10), ntw = t % 10;
         if (fits(t) && (A.M + tr - 1) / tr * (A.tiles / ntw) >= 256) return t;
@@ -895,7 +895,7 @@ static int dense_lds_tile(const DenseSplitArgs &A) {
 }
 
 template <int WR, int NTW, int NP, int NS>
-static int launch_dense_lds_ns(DenseSplitArgs A, hipStream_t st) {
+static int launch_dense_lds_ns(DenseSplitArgs A, const Tuning &T, hipStream_t st) {
     constexpr int TR = 32 * WR, NT = NTW;
     const size_t stage = (size_t)TR * 128 + (size_t)2 * NT * NP * 1024;
     const size_t pool = A.pool && TR % A.K == 0 ? (size_t)(TR / A.K) * 32 * NT * 4 : 0;
@@ -908,7 +908,7 @@ static int launch_dense_lds_ns(DenseSplitArgs A, hipStream_t st) {
     // XCD rectangles: the column split cx (1, 2, 4, 8) that holds the fewest operand bytes per
     // XCD, when the grid divides evenly (tuning dense_lds_xcd2d = 0: whole row blocks per XCD)
     A.xcx = 0;
-    if (tuning().dense_lds_xcd2d && (nr * nc) % 8 == 0) {
+    if (T.dense_lds_xcd2d && (nr * nc) % 8 == 0) {
         const int64_t abytes = (int64_t)TR * A.kb * 64, bbytes = (int64_t)32 * NT * A.kb * 16 * 2 * NP;
         int64_t best = -1;
         for (int cx = 1; cx <= 8; cx *= 2) {
@@ -924,18 +924,18 @@ static int launch_dense_lds_ns(DenseSplitArgs A, hipStream_t st) {
 
 // ring depth: tuning dense_lds_stages (2, 3 or 4; 4 only where four stages fit the CU's LDS)
 template <int WR, int NTW, int NP>
-static int launch_dense_lds(const DenseSplitArgs &A, hipStream_t st) {
+static int launch_dense_lds(const DenseSplitArgs &A, const Tuning &T, hipStream_t st) {
     constexpr size_t stage = (size_t)32 * WR * 128 + (size_t)2 * NTW * NP * 1024;
     if constexpr (4 * stage <= 160 * 1024)
-        if (tuning().dense_lds_stages >= 4) return launch_dense_lds_ns<WR, NTW, NP, 4>(A, st);
-    if (tuning().dense_lds_stages <= 2) return launch_dense_lds_ns<WR, NTW, NP, 2>(A, st);
-    return launch_dense_lds_ns<WR, NTW, NP, 3>(A, st);
+        if (T.dense_lds_stages >= 4) return launch_dense_lds_ns<WR, NTW, NP, 4>(A, T, st);
+    if (T.dense_lds_stages <= 2) return launch_dense_lds_ns<WR, NTW, NP, 2>(A, T, st);
+    return launch_dense_lds_ns<WR, NTW, NP, 3>(A, T, st);
 }
 
-static int launch_dense_lds_tile(int tile, const DenseSplitArgs &A, int np, hipStream_t st) {
+static int launch_dense_lds_tile(int tile, const DenseSplitArgs &A, int np, const Tuning &T, hipStream_t st) {
 #define PN2_LDS_NP(WR, NTW) \
-    (np == 3 ? launch_dense_lds<WR, NTW, 3>(A, st) : np == 2 ? launch_dense_lds<WR, NTW, 2>(A, st) \
-             : launch_dense_lds<WR, NTW, 1>(A, st))
+    (np == 3 ? launch_dense_lds<WR, NTW, 3>(A, T, st) : np == 2 ? launch_dense_lds<WR, NTW, 2>(A, T, st) \
+             : launch_dense_lds<WR, NTW, 1>(A, T, st))
     switch (tile) {
         case 82: return PN2_LDS_NP(8, 2);
         case 44: return PN2_LDS_NP(4, 4);
@@ -1211,8 +1211,8 @@ static size_t dense_pair_lds(const DenseSplitArgs &A0, const DenseSplitArgs &A1,
 // Whether layers A0 (group_all, first) and A1 (its consumer) run as one dense_pair_kernel
 // launch: layer 0 = 8 column tiles (256 outputs: one per wave), layer 1 reads all of them and
 // has a multiple of 8 tiles, neither pools, rows of 16-byte feature runs.
-static bool dense_pair_ok(const DenseSplitArgs &A0, const DenseSplitArgs &A1, int np0, int np1) {
-    if (!tuning().dense_pair || A0.mode != 1 || A1.mode != 0 || A0.pool || A1.pool) return false;
+static bool dense_pair_ok(const DenseSplitArgs &A0, const DenseSplitArgs &A1, int np0, int np1, const Tuning &T) {
+    if (!T.dense_pair || A0.mode != 1 || A1.mode != 0 || A0.pool || A1.pool) return false;
     if (A0.tiles != kPairWaves || A1.tiles % kPairWaves != 0 || A1.cin != 32 * A0.tiles || A1.kb != 2 * A0.tiles)
         return false;
     if (!A0.vec || !A0.feat || A0.D <= 0 || A0.D % 16 != 0 || A0.kb != 1 + A0.D / 16 || A0.C > 16) return false;
@@ -1258,79 +1258,62 @@ static int launch_dense_pair(const DenseSplitArgs &A0, const DenseSplitArgs &A1,
 // with one MFMA per product instead of six the big tile's one workgroup per CU (8 waves, 221
 // VGPRs) is load-latency bound -- STRESS (sa3 512 -> 1024 over 16384 rows, pipelined) 129.3-132.5k
 // with it, 134.1-135.6k without (interleaved A/B x3).
-static bool dense_wide(const DenseSplitArgs &A, int np) {
-    const int64_t wide_min = tuning().dense_wide_minwg;
-    return np >= 2 && A.tiles % 4 == 0 && (A.M + 255) / 256 * (A.tiles / 4) >= wide_min;
+static bool dense_wide(const DenseSplitArgs &A, int np, const Tuning &T) {
+    return np >= 2 && A.tiles % 4 == 0 && (A.M + 255) / 256 * (A.tiles / 4) >= T.dense_wide_minwg;
 }
 // the 4-wave tile's column tiles per wave: the widest that still leaves dense_minwg workgroups
-static int dense_ntc(const DenseSplitArgs &A) {
+static int dense_ntc(const DenseSplitArgs &A, const Tuning &T) {
     const int64_t rowblocks = (A.M + kDRows - 1) / kDRows;
-    const int64_t min_wg = tuning().dense_minwg;
-    for (int t = (int)tuning().dense_maxntc; t > 1; t /= 2)
-        if (A.tiles % t == 0 && rowblocks * (A.tiles / t) >= min_wg) return t;
+    for (int t = (int)T.dense_maxntc; t > 1; t /= 2)
+        if (A.tiles % t == 0 && rowblocks * (A.tiles / t) >= T.dense_minwg) return t;
     return 1;
 }
-static int dense_pool_mode(const DenseSplitArgs &A, int np) {
-    const int64_t kRowsSel = dense_wide(A, np) ? 256 : kDRows;
+static int dense_pool_mode(const DenseSplitArgs &A, int np, const Tuning &T) {
+    const int64_t kRowsSel = dense_wide(A, np, T) ? 256 : kDRows;
     if (A.K == 8 || A.K == 16) return 0;
     if (A.K % 32 == 0 && kRowsSel % A.K == 0) return 1;
     return 2;
 }
 
 // whether the layer, as it will be launched, pools through HBM atomics into a zeroed output
-static bool dense_needs_zero(const DenseSplitArgs &A, int np) {
+static bool dense_needs_zero(const DenseSplitArgs &A, int np, const Tuning &T) {
     if (!A.pool) return false;
-    const int tile = dense_lds_tile(A);
+    const int tile = dense_lds_tile(A, T);
     if (tile) return (32 * (tile / 10)) % A.K != 0;
-    return dense_pool_mode(A, np) == 2;
+    return dense_pool_mode(A, np, T) == 2;
 }
 
-static int dense_split_layer(DenseSplitArgs &A, int np, hipStream_t st, bool prezeroed = false) {
-    if (const int tile = dense_lds_tile(A)) {
-        const bool hbm = dense_needs_zero(A, np);
-        const int64_t G = A.pool ? A.M / A.K : 0, cols = 32 * (int64_t)A.tiles;
-        if (hbm && !prezeroed) {
-            hipError_t e = A.ostride == cols
-                               ? hipMemsetAsync(A.out, 0, (size_t)G * cols * 4, st)
-                               : hipMemset2DAsync(A.out, (size_t)A.ostride * 4, 0, (size_t)cols * 4, (size_t)G, st);
-            if (e != hipSuccess) return set_error(PN2_EHIP, "dense_lds: memset: %s", hipGetErrorString(e));
-        }
-        const int rc = launch_dense_lds_tile(tile, A, np, st);
-        if (rc == PN2_OK && hbm && A.norelu) {  // keys -> floats
-            hipLaunchKernelGGL(unkey_kernel, dim3((unsigned)((G * cols + 255) / 256)), dim3(256), 0, st,
-                               A.out, A.ostride, G, (int)cols);
-            PN2_LAUNCH_CHECK("unkey_kernel");
-        }
-        return rc;
-    }
-    // Large layers (e.g. translation_ssg's group_all over B*512 rows) take 256 x 128 tiles (8
-    // waves of 32 rows x 4 column tiles): the 128 x 64 tile re-reads its A rows once per 64
-    // output columns and its weights once per 128 rows, and at these sizes that L2 -> CU
-    // stream, not the MFMA, was the bound.  Only when they still leave wide_min workgroups.
-    const bool wide = dense_wide(A, np);
-    // otherwise the widest tile (NTC 32-column tiles per wave) that still leaves min_wg workgroups
-    const int ntc = dense_ntc(A);
-    if (A.pool) {
-        A.pool_mode = dense_pool_mode(A, np);
-        if (A.pool_mode == 2 && !prezeroed) {
-            const int64_t G = A.M / A.K, cols = 32 * (int64_t)A.tiles;
-            hipError_t e = A.ostride == cols
-                               ? hipMemsetAsync(A.out, 0, (size_t)G * cols * 4, st)
-                               : hipMemset2DAsync(A.out, (size_t)A.ostride * 4, 0, (size_t)cols * 4, (size_t)G, st);
-            if (e != hipSuccess) return set_error(PN2_EHIP, "dense_split: memset: %s", hipGetErrorString(e));
-        }
+template <int NTC, int NW = 4>
+static int launch_dense_split_np(const DenseSplitArgs &A, int np, hipStream_t st) {
+    return np == 1 ? launch_dense_split<NTC, 1, NW>(A, st) : np == 2 ? launch_dense_split<NTC, 2, NW>(A, st)
+                                                                     : launch_dense_split<NTC, 3, NW>(A, st);
+}
+
+static int dense_split_layer(DenseSplitArgs &A, int np, const Tuning &T, hipStream_t st, bool prezeroed = false) {
+    const int tile = dense_lds_tile(A, T);
+    if (!tile && A.pool) A.pool_mode = dense_pool_mode(A, np, T);
+    const bool hbm = dense_needs_zero(A, np, T);
+    const int64_t G = A.pool ? A.M / A.K : 0, cols = 32 * (int64_t)A.tiles;
+    if (hbm && !prezeroed) {
+        const int rc = zero_pooled_output(A.out, A.ostride, G, cols, st, tile ? "dense_lds" : "dense_split");
+        if (rc != PN2_OK) return rc;
     }
     int rc;
-    if (wide) rc = np == 1 ? launch_dense_split<4, 1, 8>(A, st) : np == 2 ? launch_dense_split<4, 2, 8>(A, st)
-                                                                         : launch_dense_split<4, 3, 8>(A, st);
-    else if (np == 1) rc = ntc == 4 ? launch_dense_split<4, 1>(A, st) : ntc == 2 ? launch_dense_split<2, 1>(A, st)
-                                                                      : launch_dense_split<1, 1>(A, st);
-    else if (np == 2) rc = ntc == 4 ? launch_dense_split<4, 2>(A, st) : ntc == 2 ? launch_dense_split<2, 2>(A, st)
-                                                                      : launch_dense_split<1, 2>(A, st);
-    else rc = ntc == 4 ? launch_dense_split<4, 3>(A, st) : ntc == 2 ? launch_dense_split<2, 3>(A, st)
-                                                           : launch_dense_split<1, 3>(A, st);
-    if (rc == PN2_OK && A.pool && A.pool_mode == 2 && A.norelu) {  // keys -> floats
-        const int64_t G = A.M / A.K, cols = 32 * (int64_t)A.tiles;
+    if (tile) {
+        rc = launch_dense_lds_tile(tile, A, np, T, st);
+    } else if (dense_wide(A, np, T)) {
+        // Large layers (e.g. translation_ssg's group_all over B*512 rows) take 256 x 128 tiles (8
+        // waves of 32 rows x 4 column tiles): the 128 x 64 tile re-reads its A rows once per 64
+        // output columns and its weights once per 128 rows, and at these sizes that L2 -> CU
+        // stream, not the MFMA, was the bound.  Only when they still leave wide_min workgroups.
+        rc = launch_dense_split_np<4, 8>(A, np, st);
+    } else {
+        // otherwise the widest tile (NTC 32-column tiles per wave) that still leaves min_wg workgroups
+        const int ntc = dense_ntc(A, T);
+        rc = ntc == 4 ? launch_dense_split_np<4>(A, np, st) : ntc == 2 ? launch_dense_split_np<2>(A, np, st)
+                                                                       : launch_dense_split_np<1>(A, np, st);
+    }
+    if (rc == PN2_OK && hbm && A.norelu) {  // keys -> floats
         hipLaunchKernelGGL(unkey_kernel, dim3((unsigned)((G * cols + 255) / 256)), dim3(256), 0, st,
                            A.out, A.ostride, G, (int)cols);
         PN2_LAUNCH_CHECK("unkey_kernel");
@@ -1338,19 +1321,25 @@ static int dense_split_layer(DenseSplitArgs &A, int np, hipStream_t st, bool pre
     return rc;
 }
 
-// The chain kernel's layer-0 pre-pass (sa_chain.hip, KB0M < 0): z[b*N + n][c] = sum_k W0[c][k] *
-// x_k(b, n) over the raw [xyz | features] row of every source point (no bias / BN / ReLU), with
-// the fp32-accurate split products.  z is [B*N][cout0] fp32 at `z` (16-byte aligned).
-int launch_layer0_prepass(const pn2_sa_src &s, const pn2_mlp_layer &L0, float *z, hipStream_t st) {
-    DenseSplitArgs A;
-    memset(&A, 0, sizeof(A));
+// a first layer over the source's points: rows [xyz | features] of every point (group_all, and
+// the chain's pre-pass)
+static void points_source(DenseSplitArgs &A, const pn2_sa_src &s, const pn2_mlp_layer &L0) {
     A.mode = 1;
     A.pts = s.pts; A.pb = s.pb; A.pn = s.pn; A.pc = s.pc;
     A.feat = s.feat; A.fb = s.fb; A.fn = s.fn;
     A.N = (int)s.N; A.C = (int)s.C; A.D = (int)s.D;
-    A.vec = (s.D == 0 || (s.D % 4 == 0 && ((uintptr_t)s.feat & 15) == 0 && s.fn % 4 == 0 &&
-                          s.fb % 4 == 0)) ? 1 : 0;
+    A.vec = rows_16b(s.feat, s.D, s.fn, s.fb, true) ? 1 : 0;
     A.kb = (int)pn2_layer_split_kblocks(L0.cin, s.C);
+}
+
+// The chain kernel's layer-0 pre-pass (sa_chain.hip, KB0M < 0): z[b*N + n][c] = sum_k W0[c][k] *
+// x_k(b, n) over the raw [xyz | features] row of every source point (no bias / BN / ReLU), with
+// the fp32-accurate split products.  z is [B*N][cout0] fp32 at `z` (16-byte aligned).
+int launch_layer0_prepass(const pn2_sa_src &s, const pn2_mlp_layer &L0, float *z, const Tuning &T,
+                          hipStream_t st) {
+    DenseSplitArgs A;
+    memset(&A, 0, sizeof(A));
+    points_source(A, s, L0);
     A.w = reinterpret_cast<const bf16x8 *>(L0.wt_split);
     A.tiles = (int)(L0.cout / 32);
     A.M = (int)(s.B * s.N);
@@ -1359,152 +1348,172 @@ int launch_layer0_prepass(const pn2_sa_src &s, const pn2_mlp_layer &L0, float *z
     A.raw = 1;
     // split fp16 with the scale from each 32-point block's own [xyz | features] (a cloud's points
     // fill whole blocks); tuning dense_f16 = 0: split bf16
-    if (tuning().dense_f16 >= 2 && s.N % 32 == 0) {
+    if (T.dense_f16 >= 2 && s.N % 32 == 0) {
         A.w = split_f16_planes(L0.wt_split, L0.cout, A.kb);
         A.wscale = split_f16_inv_scale(L0.wt_split, L0.cout, A.kb);
-        return dense_split_layer(A, 2, st);
+        return dense_split_layer(A, 2, T, st);
     }
-    return dense_split_layer(A, 3, st);
+    return dense_split_layer(A, 3, T, st);
 }
 
-static thread_local int g_dense_planes = 3;
-int dense_last_planes() { return g_dense_planes; }
+// ------------------------------------------------------------------ layer-by-layer chains
+// group_all / dense-row chains, one launch per layer (or one for group_all's first two); hidden
+// outputs ping-pong through the two halves of the workspace.
+struct DensePlan {
+    int64_t w = 0;  // widest hidden layer, rounded to 4 floats (0: not eligible; 1: one layer)
+    // Workspace: two [Mp][w] fp32 halves, then two [nrb][tw] uint max tables (the split-fp16
+    // layers' activation scales, split_bf16.h).  A chain of several layers without it is not
+    // eligible.
+    int64_t Mp = 0, nrb = 0, tw = 0, bytes = 0;
+    int np[4] = {0, 0, 0, 0};  // planes per operand of each layer
+    bool frag[5] = {false, false, false, false, false};  // layer reads fragment-ordered rows
+    bool fold_zero = false;    // the layer before the last zeroes the last one's atomicMax pool
+    bool pair = false;         // group_all's first two layers as one launch
+    int planes = 0;            // the planes carrying most of the flops
+};
 
-// Workspace of the layer-by-layer path: two [M][w] fp32 halves, then two [ceil(M/32)][w/32]
-// uint max tables (the split-fp16 layers' activation scales, split_bf16.h)
-int64_t dense_split_ws_bytes(int64_t M, int64_t w) {
-    const int64_t Mp = (M + 31) / 32 * 32;  // fragment-ordered halves cover whole row blocks
-    return 2 * Mp * w * 4 + 2 * (Mp / 32) * ((w + 31) / 32) * 4;
+// Layer l's kernel arguments.  ws: the workspace, or null while planning -- which kernel a layer
+// takes depends on shapes and on the source's pointers only (every workspace row is 16-byte
+// aligned).
+static DenseSplitArgs dense_layer_args(const MlpCall &c, const DensePlan &P, int l, float *ws) {
+    const pn2_sa_src &s = c.s;
+    const pn2_mlp_layer *layers = c.layers;
+    const int nlayers = c.nlayers;
+    const bool last = l == nlayers - 1;
+    auto half = [&](int i) { return ws ? ws + i * P.Mp * P.w : nullptr; };
+    auto maxtab = [&](int i) { return ws ? reinterpret_cast<unsigned *>(ws + 2 * P.Mp * P.w) + i * P.nrb * P.tw : nullptr; };
+    DenseSplitArgs A;
+    memset(&A, 0, sizeof(A));
+    if (l == 0 && s.mode == PN2_SRC_GROUP_ALL) {
+        points_source(A, s, layers[0]);
+    } else {
+        A.mode = 0;
+        if (l == 0) {
+            A.rows = s.rows;
+            A.rs = s.rs;
+        } else {
+            A.rows = half((l - 1) & 1);
+            A.rs = P.w;
+        }
+        A.cin = (int)layers[l].cin;
+        A.vec = (((uintptr_t)A.rows & 15) == 0 && A.rs % 4 == 0) ? 1 : 0;
+        A.kb = (int)((layers[l].cin + 15) / 16);
+    }
+    A.w = reinterpret_cast<const bf16x8 *>(layers[l].wt_split);
+    A.alpha = layers[l].alpha;
+    A.beta = layers[l].beta;
+    A.tiles = (int)(layers[l].cout / 32);
+    A.M = (int)c.M;
+    if (P.np[l] == 2) {
+        A.w = split_f16_planes(layers[l].wt_split, layers[l].cout, A.kb);
+        A.wscale = split_f16_inv_scale(layers[l].wt_split, layers[l].cout, A.kb);
+        if (l > 0) {
+            A.in_max = maxtab((l - 1) & 1);
+            A.in_tiles = (int)(layers[l - 1].cout / 32);
+        }
+    }
+    if (!last && P.np[l + 1] == 2) A.out_max = maxtab(l & 1);
+    A.pool = last ? c.pool : 0;
+    A.norelu = (layers[l].flags & PN2_LAYER_NO_RELU) ? 1 : 0;
+    A.K = (int)c.K;
+    A.out = last ? c.out : half(l & 1);
+    A.ostride = last ? c.ostride : P.w;
+    // hidden rows in fragment order where their consumer is the register-staged kernel
+    if (l >= 1 && P.frag[l]) A.frag_in = 1, A.vec = 1;
+    if (!last && P.frag[l + 1]) A.frag_out = 1;
+    return A;
 }
 
-// Widest hidden layer of a chain the split dense path runs layer by layer (0: not eligible).
-int64_t dense_split_width(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int np) {
-    if (np == 3 && tuning().mlp_f32) return 0;
-    if (s.mode != PN2_SRC_GROUP_ALL && s.mode != PN2_SRC_ROWS) return 0;
-    if (s.mode == PN2_SRC_GROUP_ALL && s.C > 16) return 0;
+static DensePlan plan_dense(const MlpCall &c) {
+    DensePlan P;
+    const pn2_sa_src &s = c.s;
+    const pn2_mlp_layer *layers = c.layers;
+    const int nlayers = c.nlayers, np = c.np;
+    const Tuning &T = c.T;
+    if (np == 3 && T.mlp_f32) return P;
+    if (s.mode != PN2_SRC_GROUP_ALL && s.mode != PN2_SRC_ROWS) return P;
+    if (s.mode == PN2_SRC_GROUP_ALL && s.C > 16) return P;
     int64_t w = 0;
     for (int l = 0; l < nlayers; ++l) {
-        if (!layers[l].wt_split || ((uintptr_t)layers[l].wt_split & 15)) return 0;
+        if (!layers[l].wt_split || ((uintptr_t)layers[l].wt_split & 15)) return P;
         if (l < nlayers - 1) w = std::max(w, layers[l].cout);
     }
-    return nlayers > 1 ? (w + 3) / 4 * 4 : 1;
-}
-
-// 1: launched, 0: not eligible, <0: error.  Layers run one by one; hidden outputs ping-pong
-// through the two [M][w] halves of the workspace.
-int try_launch_dense_split(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers, int pool,
-                           float *out, int64_t ostride, float *ws, int64_t ws_bytes, int64_t M,
-                           int64_t K, int np, hipStream_t st) {
-    const int64_t w = dense_split_width(s, layers, nlayers, np);
-    if (w == 0) return 0;
-    if (nlayers > 1 && (!ws || ws_bytes < dense_split_ws_bytes(M, w) || ((uintptr_t)ws & 15))) return 0;
+    P.w = nlayers > 1 ? (w + 3) / 4 * 4 : 1;
+    P.tw = (P.w + 31) / 32, P.nrb = (c.M + 31) / 32;
+    P.Mp = P.nrb * 32;  // fragment-ordered halves cover whole row blocks
+    if (nlayers > 1) P.bytes = 2 * P.Mp * P.w * 4 + 2 * P.nrb * P.tw * 4;
     // The fp32-accurate hidden layers after the first (their rows are the workspace rows the
     // layer before wrote, with its per-block maxima) run split fp16 (3 MFMAs per product);
     // the first layer keeps split bf16 (its input comes from outside: no maxima).  A cloud's rows
     // must start at a 32-row block (K % 32 == 0) so its scale never depends on other clouds.
     // Tuning dense_f16 = 0: split bf16 everywhere.
-    const bool f16 = np == 3 && tuning().dense_f16 && K % 32 == 0;
-    const int64_t tw = (w + 31) / 32, nrb = (M + 31) / 32, Mp = nrb * 32;
-    unsigned *maxtab = nlayers > 1 ? reinterpret_cast<unsigned *>(ws + 2 * Mp * w) : nullptr;
+    const bool f16 = np == 3 && T.dense_f16 && c.K % 32 == 0;
     // the first layer over points (group_all) takes its scale from its own rows when a cloud's
     // points fill whole 32-row blocks
-    const bool f16_first = f16 && tuning().dense_f16 >= 2 && s.mode == PN2_SRC_GROUP_ALL && s.N % 32 == 0;
-    auto layer_np = [&](int l) { return (f16 && l >= 1) || (f16_first && l == 0) ? 2 : np; };
-    auto make = [&](int l) {
-        const bool last = l == nlayers - 1;
-        DenseSplitArgs A;
-        memset(&A, 0, sizeof(A));
-        if (l == 0 && s.mode == PN2_SRC_GROUP_ALL) {
-            A.mode = 1;
-            A.pts = s.pts; A.pb = s.pb; A.pn = s.pn; A.pc = s.pc;
-            A.feat = s.feat; A.fb = s.fb; A.fn = s.fn;
-            A.N = (int)s.N; A.C = (int)s.C; A.D = (int)s.D;
-            A.vec = (s.D == 0 || (s.D % 4 == 0 && ((uintptr_t)s.feat & 15) == 0 && s.fn % 4 == 0 &&
-                                  s.fb % 4 == 0)) ? 1 : 0;
-            A.kb = (int)pn2_layer_split_kblocks(layers[0].cin, s.C);
-        } else {
-            A.mode = 0;
-            if (l == 0) {
-                A.rows = s.rows;
-                A.rs = s.rs;
-            } else {
-                A.rows = ws + ((l - 1) & 1) * Mp * w;
-                A.rs = w;
-            }
-            A.cin = (int)layers[l].cin;
-            A.vec = (((uintptr_t)A.rows & 15) == 0 && A.rs % 4 == 0) ? 1 : 0;
-            A.kb = (int)((layers[l].cin + 15) / 16);
-        }
-        A.w = reinterpret_cast<const bf16x8 *>(layers[l].wt_split);
-        A.alpha = layers[l].alpha;
-        A.beta = layers[l].beta;
-        A.tiles = (int)(layers[l].cout / 32);
-        A.M = (int)M;
-        if (layer_np(l) == 2) {
-            A.w = split_f16_planes(layers[l].wt_split, layers[l].cout, A.kb);
-            A.wscale = split_f16_inv_scale(layers[l].wt_split, layers[l].cout, A.kb);
-            if (l > 0) {
-                A.in_max = maxtab + ((l - 1) & 1) * nrb * tw;
-                A.in_tiles = (int)(layers[l - 1].cout / 32);
-            }
-        }
-        if (l < nlayers - 1 && layer_np(l + 1) == 2) A.out_max = maxtab + (l & 1) * nrb * tw;
-        A.pool = last ? pool : 0;
-        A.norelu = (layers[l].flags & PN2_LAYER_NO_RELU) ? 1 : 0;
-        A.K = (int)K;
-        A.out = last ? out : ws + (l & 1) * Mp * w;
-        A.ostride = last ? ostride : w;
-        return A;
-    };
-    // hidden rows in fragment order where their consumer is the register-staged kernel (the
-    // LDS-staged one DMAs whole row lines); tuning dense_frag = 0: row-major everywhere
-    bool frag[5] = {false, false, false, false, false};
-    for (int l = 1; l < nlayers && l < 5; ++l) frag[l] = tuning().dense_frag && dense_lds_tile(make(l)) == 0;
-    auto make_f = [&](int l) {
-        DenseSplitArgs A = make(l);
-        if (l >= 1 && frag[l]) A.frag_in = 1, A.vec = 1;
-        if (l + 1 < nlayers && l + 1 < 5 && frag[l + 1]) A.frag_out = 1;
-        return A;
-    };
-    // a last layer that pools by HBM atomics gets its output zeroed by the layer before it
-    // (one launch fewer than a memset: PointNet-v1's max over N points, group_all over K > 256)
-    DenseSplitArgs last = make_f(nlayers - 1);
-    const bool fold_zero = nlayers > 1 && last.pool && dense_needs_zero(last, layer_np(nlayers - 1));
-    if (s.zero_out && s.zero_count > 0) {  // the caller's side job rides on the last layer
-        last.zero = s.zero_out;
-        last.zrows = 1;
-        last.zcols = s.zero_count;
-        last.zstride = s.zero_count;
-    }
-    auto args_of = [&](int l) {
-        DenseSplitArgs A = l == nlayers - 1 ? last : make_f(l);
-        if (fold_zero && l == nlayers - 2) {
-            A.zero = last.out;
-            A.zrows = last.M / last.K;
-            A.zcols = 32 * (int64_t)last.tiles;
-            A.zstride = last.ostride;
-        }
-        return A;
-    };
+    const bool f16_first = f16 && T.dense_f16 >= 2 && s.mode == PN2_SRC_GROUP_ALL && s.N % 32 == 0;
     int64_t flops[4] = {0, 0, 0, 0};
     for (int l = 0; l < nlayers; ++l) {
-        flops[layer_np(l)] += layers[l].cin * layers[l].cout;
-        DenseSplitArgs A = args_of(l);
-        if (l == 0 && nlayers > 1) {  // group_all's first two layers as one launch
-            DenseSplitArgs B = args_of(1);
-            B.frag_in = 0;  // its input never leaves the CU
-            if (dense_pair_ok(A, B, layer_np(0), layer_np(1))) {
-                const int rc = launch_dense_pair(A, B, layer_np(0), layer_np(1), st);
-                if (rc != PN2_OK) return rc;
-                flops[layer_np(1)] += layers[1].cin * layers[1].cout;
-                l = 1;
-                continue;
-            }
+        P.np[l] = (f16 && l >= 1) || (f16_first && l == 0) ? 2 : np;
+        flops[P.np[l]] += layers[l].cin * layers[l].cout;
+    }
+    P.planes = flops[2] > flops[np] ? 2 : np;
+    // fragment order where the consumer is the register-staged kernel (the LDS-staged one DMAs
+    // whole row lines); tuning dense_frag = 0: row-major everywhere.  (Ascending: layer l's
+    // arguments read frag[l] and frag[l + 1], both still unset.)
+    for (int l = 1; l < nlayers; ++l)
+        P.frag[l] = T.dense_frag && dense_lds_tile(dense_layer_args(c, P, l, nullptr), T) == 0;
+    if (nlayers > 1) {
+        // a last layer that pools by HBM atomics gets its output zeroed by the layer before it
+        // (one launch fewer than a memset: PointNet-v1's max over N points, group_all over K > 256)
+        const DenseSplitArgs last = dense_layer_args(c, P, nlayers - 1, nullptr);
+        P.fold_zero = last.pool && dense_needs_zero(last, P.np[nlayers - 1], T);
+        DenseSplitArgs B = dense_layer_args(c, P, 1, nullptr);
+        B.frag_in = 0;  // its input never leaves the CU
+        P.pair = dense_pair_ok(dense_layer_args(c, P, 0, nullptr), B, P.np[0], P.np[1], T);
+    }
+    return P;
+}
+
+int64_t dense_ws_bytes(const MlpCall &c) { return plan_dense(c).bytes; }
+
+// 1: launched, 0: not eligible, <0: error
+int try_launch_dense(const MlpCall &c, MlpReport &r) {
+    const DensePlan P = plan_dense(c);
+    if (P.w == 0) return 0;
+    if (P.bytes && !ws_fits(c.ws, c.ws_bytes, P.bytes)) return 0;
+    const pn2_sa_src &s = c.s;
+    const int nlayers = c.nlayers;
+    auto args_of = [&](int l) {
+        DenseSplitArgs A = dense_layer_args(c, P, l, c.ws);
+        if (l == nlayers - 1 && s.zero_out && s.zero_count > 0) {  // the caller's side job rides on the last layer
+            A.zero = s.zero_out;
+            A.zrows = 1;
+            A.zcols = s.zero_count;
+            A.zstride = s.zero_count;
         }
-        const int rc = dense_split_layer(A, layer_np(l), st, fold_zero && l == nlayers - 1);
+        if (P.fold_zero && l == nlayers - 2) {  // the last layer's pooled output
+            A.zero = c.out;
+            A.zrows = c.M / c.K;
+            A.zcols = c.layers[nlayers - 1].cout;
+            A.zstride = c.ostride;
+        }
+        return A;
+    };
+    for (int l = 0; l < nlayers; ++l) {
+        DenseSplitArgs A = args_of(l);
+        int rc;
+        if (l == 0 && P.pair) {
+            DenseSplitArgs B = args_of(1);
+            B.frag_in = 0;
+            rc = launch_dense_pair(A, B, P.np[0], P.np[1], c.st);
+            l = 1;
+        } else {
+            rc = dense_split_layer(A, P.np[l], c.T, c.st, P.fold_zero && l == nlayers - 1);
+        }
         if (rc != PN2_OK) return rc;
     }
-    g_dense_planes = flops[2] > flops[np] ? 2 : np;
+    r.path = PN2_PATH_SPLIT_BF16;
+    r.planes = P.planes;
     return 1;
 }
 

@@ -652,7 +652,7 @@ static int make_plan(Plan &P, const pn2_sa_src &s, const pn2_mlp_layer *layers, 
     const float *fp = s.mode == PN2_SRC_ROWS ? s.rows : s.feat;
     const int64_t fr = s.mode == PN2_SRC_ROWS ? s.rs : s.fn;
     const int64_t fb = s.mode == PN2_SRC_ROWS ? 0 : s.fb;
-    A.vec_feat = (D > 0 && D % 4 == 0 && ((uintptr_t)fp & 15) == 0 && fr % 4 == 0 && fb % 4 == 0) ? 1 : 0;
+    A.vec_feat = rows_16b(fp, D, fr, fb, false) ? 1 : 0;
 
     // dense kernel: a single layer over dense rows / group_all whose input is wide (no gather
     // tables needed, A streams through LDS in k chunks)
@@ -732,13 +732,8 @@ static int try_launch(const Plan &P, hipStream_t st) {
     if (P.A.pool && P.A.pool_mode != 0 && (P.A.pool_mode == 2 || (P.BM && P.BM % P.A.K != 0))) {
         // groups straddle workgroups: merged with atomicMax into a zeroed output
         const int64_t coutL = (int64_t)P.A.ycols * P.ysplit;
-        const int64_t G = P.A.M / P.A.K;
-        hipError_t e = (P.A.ostride == coutL)
-                           ? hipMemsetAsync(P.A.out, 0, (size_t)G * coutL * 4, st)
-                           : hipMemset2DAsync(P.A.out, (size_t)P.A.ostride * 4, 0, (size_t)coutL * 4,
-                                              (size_t)G, st);
-        if (e != hipSuccess)
-            return set_error(PN2_EHIP, "pn2_sa_mlp_max_f32: memset: %s", hipGetErrorString(e));
+        const int zrc = zero_pooled_output(P.A.out, P.A.ostride, P.A.M / P.A.K, coutL, st, "pn2_sa_mlp_max_f32");
+        if (zrc != PN2_OK) return zrc;
     }
     int rc = PN2_EUNSUPPORTED;
 #define PN2_GO128(a, b, c, d) \
@@ -754,65 +749,26 @@ static int try_launch(const Plan &P, hipStream_t st) {
     return rc == PN2_OK ? 1 : rc;
 }
 
-static int validate(const pn2_sa_src *src, const pn2_mlp_layer *layers, int nlayers,
-                    int64_t &M, int64_t &K) {
-    PN2_REQUIRE(src && layers, "pn2_sa_mlp_max_f32: null pointer");
-    PN2_REQUIRE(nlayers >= 1 && nlayers <= kMaxLayers, "pn2_sa_mlp_max_f32: nlayers=%d", nlayers);
-    const pn2_sa_src &s = *src;
-    int64_t cin0 = 0;
-    switch (s.mode) {
-    case PN2_SRC_GROUP_XYZ_FIRST:
-    case PN2_SRC_GROUP_FEAT_FIRST:
-        PN2_REQUIRE(s.pts && s.ctr && (s.idx || s.idx32) && (s.D == 0 || s.feat), "pn2_sa_mlp_max_f32: group source");
-        PN2_REQUIRE(s.B >= 0 && s.N >= 1 && s.S >= 1 && s.K >= 1 && s.C >= 1 && s.D >= 0,
-                    "pn2_sa_mlp_max_f32: bad group shape");
-        M = s.B * s.S * s.K; cin0 = s.C + s.D; K = s.K;
-        break;
-    case PN2_SRC_GROUP_ALL:
-        PN2_REQUIRE(s.pts && (s.D == 0 || s.feat), "pn2_sa_mlp_max_f32: group_all source");
-        PN2_REQUIRE(s.B >= 0 && s.N >= 1 && s.C >= 1 && s.D >= 0, "pn2_sa_mlp_max_f32: bad group_all shape");
-        M = s.B * s.N; cin0 = s.C + s.D; K = s.N;
-        break;
-    case PN2_SRC_ROWS:
-        PN2_REQUIRE(s.rows && s.rs >= layers[0].cin, "pn2_sa_mlp_max_f32: rows source");
-        PN2_REQUIRE(s.B >= 0 && s.S >= 1 && s.K >= 1, "pn2_sa_mlp_max_f32: bad rows shape");
-        M = s.B * s.S * s.K; cin0 = layers[0].cin; K = s.K;
-        break;
-    default:
-        return set_error(PN2_EINVAL, "pn2_sa_mlp_max_f32: mode %d", s.mode);
-    }
-    PN2_REQUIRE(M < (int64_t(1) << 31), "pn2_sa_mlp_max_f32: %lld rows exceed 2^31", (long long)M);
-    PN2_REQUIRE(layers[0].cin == cin0, "pn2_sa_mlp_max_f32: layer0 cin %lld != source width %lld",
-                (long long)layers[0].cin, (long long)cin0);
-    for (int l = 0; l < nlayers; ++l) {
-        const pn2_mlp_layer &q = layers[l];
-        PN2_REQUIRE(q.wt && q.alpha && q.beta, "pn2_sa_mlp_max_f32: layer %d null", l);
-        PN2_REQUIRE(q.cout % 32 == 0 && q.cout >= 32,
-                    "pn2_sa_mlp_max_f32: layer %d cout=%lld not a multiple of 32", l, (long long)q.cout);
-        if (l > 0)
-            PN2_REQUIRE(q.cin == layers[l - 1].cout, "pn2_sa_mlp_max_f32: layer %d cin mismatch", l);
-    }
-    return PN2_OK;
-}
 
+// ------------------------------------------------------------------ fp32 plan
 // A chain runs as consecutive fused segments; a segment ends after a layer wider than one
 // column slice (its output cannot stay in LDS) or at the end of the chain.  Segment outputs
 // go to two ping-pong [M][w] workspace buffers.  A segment with no compiled kernel runs layer
 // by layer through the same workspace.
+struct F32Plan {
+    int nseg = 0;
+    struct { int l0, l1; bool fused; } seg[kMaxLayers];  // layers l0..l1 inclusive
+    // workspace row width: the widest layer output that has to round-trip through HBM (rounded
+    // to 4 floats so every workspace row is 16-byte aligned)
+    int64_t w = 0;
+};
+
 static int seg_end(const pn2_mlp_layer *layers, int nlayers, int l0) {
     // a layer wider than one column slice runs alone (its columns split over grid.y)
     if (layers[l0].cout > kMaxSlice) return l0;
     int l = l0;
     while (l < nlayers - 1 && layers[l + 1].cout <= kMaxSlice) ++l;
     return l;  // inclusive
-}
-
-static bool segment_ok(const pn2_sa_src &s, const pn2_mlp_layer *layers, int l0, int l1,
-                       int64_t M, int64_t K, int pool) {
-    Plan P;
-    if (make_plan(P, s, layers + l0, l1 - l0 + 1, pool, nullptr, layers[l1].cout, M, K) != PN2_OK)
-        return false;
-    return has_kernel(P);
 }
 
 static pn2_sa_src rows_src(const float *rows, int64_t w, int64_t M, int64_t K) {
@@ -825,32 +781,27 @@ static pn2_sa_src rows_src(const float *rows, int64_t w, int64_t M, int64_t K) {
     return nx;
 }
 
-// workspace row width: the widest layer output that has to round-trip through HBM (rounded
-// to 4 floats so every workspace row is 16-byte aligned)
-static int64_t workspace_width(const pn2_sa_src &s, const pn2_mlp_layer *layers, int nlayers,
-                               int64_t M, int64_t K) {
-    int64_t w = 0;
-    for (int l0 = 0; l0 < nlayers;) {
-        const int l1 = seg_end(layers, nlayers, l0);
-        const bool last_seg = l1 == nlayers - 1;
-        pn2_sa_src src = s;
-        if (l0 > 0) src = rows_src(reinterpret_cast<const float *>(256), 1024, M, K);
-        if (!segment_ok(src, layers, l0, l1, M, K, last_seg ? 1 : 0))
-            for (int l = l0; l < l1; ++l) w = std::max(w, layers[l].cout);
-        if (!last_seg) w = std::max(w, layers[l1].cout);
+static F32Plan plan_f32(const MlpCall &c) {
+    F32Plan F;
+    for (int l0 = 0; l0 < c.nlayers;) {
+        const int l1 = seg_end(c.layers, c.nlayers, l0);
+        const bool last_seg = l1 == c.nlayers - 1;
+        // (which kernel a segment over workspace rows takes does not depend on where they are)
+        Plan P;
+        const bool fused = make_plan(P, l0 ? rows_src(nullptr, 4, c.M, c.K) : c.s, c.layers + l0, l1 - l0 + 1,
+                                     last_seg ? c.pool : 0, nullptr, c.layers[l1].cout, c.M, c.K) == PN2_OK &&
+                           has_kernel(P);
+        F.seg[F.nseg++] = {l0, l1, fused};
+        if (!fused)
+            for (int l = l0; l < l1; ++l) F.w = std::max(F.w, c.layers[l].cout);
+        if (!last_seg) F.w = std::max(F.w, c.layers[l1].cout);
         l0 = l1 + 1;
     }
-    return (w + 3) / 4 * 4;
+    F.w = (F.w + 3) / 4 * 4;
+    return F;
 }
 
-extern "C" int64_t pn2_sa_mlp_workspace_bytes(const pn2_sa_src *src, const pn2_mlp_layer *layers,
-                                              int nlayers) {
-    int64_t M = 0, K = 1;
-    if (validate(src, layers, nlayers, M, K) != PN2_OK) return -1;
-    const int64_t ds = nlayers > 1 ? dense_split_width(*src, layers, nlayers, 3) : 0;
-    return std::max({dense_split_ws_bytes(M, ds), 2 * M * workspace_width(*src, layers, nlayers, M, K) * 4,
-                     chain_prepass_bytes(*src, layers, nlayers, 3)});
-}
+int64_t pn2::f32_ws_bytes(const MlpCall &c) { return 2 * c.M * plan_f32(c).w * 4; }
 
 static int run_plan(const pn2_sa_src &cur, const pn2_mlp_layer *layers, int l0, int l1, int pool,
                     float *dst, int64_t ostride, int64_t M, int64_t K, hipStream_t st) {
@@ -865,154 +816,33 @@ static int run_plan(const pn2_sa_src &cur, const pn2_mlp_layer *layers, int l0, 
     return PN2_OK;
 }
 
-static thread_local int g_last_path = 0;
-static thread_local int g_last_planes = 0;  // planes per operand of the call's MLP kernels
-extern "C" int pn2_sa_mlp_last_path(void) { return g_last_path; }
-extern "C" int pn2_sa_mlp_last_planes(void) { return g_last_planes; }
-static thread_local int g_last_side = -1;  // pn2_sa_mlp_last_fps_side
-extern "C" int pn2_sa_mlp_last_fps_side(void) { return g_last_side; }
-
-// the src's zero side job on the paths whose kernels do not take it (the dense-layer path's
-// last layer does)
-static int zero_side_job(const pn2_sa_src &s, hipStream_t st) {
-    if (!s.zero_out || s.zero_count <= 0) return PN2_OK;
-    const hipError_t e = hipMemsetAsync(s.zero_out, 0, (size_t)s.zero_count * 4, st);
-    return e == hipSuccess ? PN2_OK : set_error(PN2_EHIP, "pn2_sa_mlp_max: zero_out: %s", hipGetErrorString(e));
-}
-
-static int mlp_max_f32(const pn2_sa_src *src, const pn2_mlp_layer *layers,
-                       int nlayers, int pool, float *out, int64_t ostride,
-                       float *workspace, int64_t workspace_bytes, void *stream) {
-    int64_t M = 0, K = 1;
-    int rc = validate(src, layers, nlayers, M, K);
-    if (rc != PN2_OK) return rc;
-    PN2_REQUIRE(out, "pn2_sa_mlp_max_f32: null out");
-    PN2_REQUIRE(ostride >= layers[nlayers - 1].cout, "pn2_sa_mlp_max_f32: ostride");
-    if (M == 0) return PN2_OK;
-    if (pool) PN2_REQUIRE(M % K == 0, "pn2_sa_mlp_max_f32: rows not a multiple of the group size");
-    hipStream_t st = as_stream(stream);
-    rc = try_launch_chain(*src, layers, nlayers, pool, out, ostride, M, K, 3, workspace,
-                          workspace_bytes, st);
-    if (rc != 0) {
-        if (rc > 0) g_last_path = PN2_PATH_SPLIT_BF16, g_last_planes = chain_last_planes();
-        return rc < 0 ? rc : zero_side_job(*src, st);
-    }
-    rc = try_launch_dense_split(*src, layers, nlayers, pool, out, ostride, workspace, workspace_bytes,
-                                M, K, 3, st);
-    if (rc != 0) {
-        if (rc > 0) g_last_path = PN2_PATH_SPLIT_BF16, g_last_planes = dense_last_planes();
-        return rc < 0 ? rc : PN2_OK;
-    }
-    if ((rc = zero_side_job(*src, st)) != PN2_OK) return rc;
-    for (int l = 0; l < nlayers; ++l)
+// every chain the validation admits runs here or fails: 1 launched, <0 error
+int pn2::try_launch_f32(const MlpCall &c, MlpReport &r) {
+    const pn2_mlp_layer *layers = c.layers;
+    for (int l = 0; l < c.nlayers; ++l)
         if (layers[l].flags & PN2_LAYER_NO_RELU)
             return set_error(PN2_EUNSUPPORTED, "pn2_sa_mlp_max_f32: layer %d without ReLU needs the split "
                              "dense-layer path (group_all / rows source, split weight images)", l);
-    g_last_path = PN2_PATH_F32;
-    g_last_planes = 0;
-    const int64_t w = workspace_width(*src, layers, nlayers, M, K);
+    const F32Plan F = plan_f32(c);
+    const int64_t M = c.M, w = F.w;
     if (w > 0)
-        PN2_REQUIRE(workspace && workspace_bytes >= 2 * M * w * 4 && ((uintptr_t)workspace & 15) == 0,
+        PN2_REQUIRE(ws_fits(c.ws, c.ws_bytes, 2 * M * w * 4),
                     "pn2_sa_mlp_max_f32: this layer chain needs a 16-byte aligned %lld-byte workspace",
                     (long long)(2 * M * w * 4));
-    pn2_sa_src cur = *src;
+    pn2_sa_src cur = c.s;
     int buf = 0;
-    for (int l0 = 0; l0 < nlayers;) {
-        const int l1 = seg_end(layers, nlayers, l0);
-        const bool last_seg = l1 == nlayers - 1;
-        if (segment_ok(cur, layers, l0, l1, M, K, last_seg ? pool : 0)) {
-            float *dst = last_seg ? out : workspace + buf * M * w;
-            rc = run_plan(cur, layers, l0, l1, last_seg ? pool : 0, dst, last_seg ? ostride : w, M, K, st);
+    for (int i = 0; i < F.nseg; ++i)
+        // a fused segment is one launch, any other one launch per layer
+        for (int l0 = F.seg[i].l0; l0 <= F.seg[i].l1;) {
+            const int l1 = F.seg[i].fused ? F.seg[i].l1 : l0;
+            const bool last = l1 == c.nlayers - 1;
+            float *dst = last ? c.out : c.ws + buf * M * w;
+            const int rc = run_plan(cur, layers, l0, l1, last ? c.pool : 0, dst, last ? c.ostride : w, M, c.K, c.st);
             if (rc != PN2_OK) return rc;
-            if (!last_seg) { cur = rows_src(dst, w, M, K); buf ^= 1; }
-        } else {
-            for (int l = l0; l <= l1; ++l) {
-                const bool last = l == nlayers - 1;
-                float *dst = last ? out : workspace + buf * M * w;
-                rc = run_plan(cur, layers, l, l, last ? pool : 0, dst, last ? ostride : w, M, K, st);
-                if (rc != PN2_OK) return rc;
-                if (!last) { cur = rows_src(dst, w, M, K); buf ^= 1; }
-            }
+            if (!last) { cur = rows_src(dst, w, M, c.K); buf ^= 1; }
+            l0 = l1 + 1;
         }
-        l0 = l1 + 1;
-    }
-    return PN2_OK;
-}
-
-// bf16 arithmetic (BASELINE config 5, the large-N stress run): the same fused kernels with one
-// bf16 plane per operand -- activations rounded to bf16 (round-to-nearest-even) where a layer
-// reads them, weights = the hi plane of the split image, products exact, fp32 accumulation,
-// BN / ReLU / max in fp32, fp32 output.  No fp32 fallback: a chain neither the chain kernel nor
-// the dense-layer kernel covers is PN2_EUNSUPPORTED.
-extern "C" int64_t pn2_sa_mlp_workspace_bytes_bf16(const pn2_sa_src *src,
-                                                   const pn2_mlp_layer *layers, int nlayers) {
-    int64_t M = 0, K = 1;
-    if (validate(src, layers, nlayers, M, K) != PN2_OK) return -1;
-    const int64_t ds = nlayers > 1 ? dense_split_width(*src, layers, nlayers, 1) : 0;
-    return std::max(ds ? dense_split_ws_bytes(M, ds) : 0, chain_prepass_bytes(*src, layers, nlayers, 1));
-}
-
-static int mlp_max_bf16(const pn2_sa_src *src, const pn2_mlp_layer *layers,
-                        int nlayers, int pool, float *out, int64_t ostride,
-                        float *workspace, int64_t workspace_bytes, void *stream) {
-    int64_t M = 0, K = 1;
-    int rc = validate(src, layers, nlayers, M, K);
-    if (rc != PN2_OK) return rc;
-    PN2_REQUIRE(out, "pn2_sa_mlp_max_bf16: null out");
-    PN2_REQUIRE(ostride >= layers[nlayers - 1].cout, "pn2_sa_mlp_max_bf16: ostride");
-    for (int l = 0; l < nlayers; ++l)
-        PN2_REQUIRE(layers[l].wt_split && ((uintptr_t)layers[l].wt_split & 15) == 0,
-                    "pn2_sa_mlp_max_bf16: layer %d needs its 16-byte aligned split weight image", l);
-    if (M == 0) return PN2_OK;
-    if (pool) PN2_REQUIRE(M % K == 0, "pn2_sa_mlp_max_bf16: rows not a multiple of the group size");
-    hipStream_t st = as_stream(stream);
-    rc = try_launch_chain(*src, layers, nlayers, pool, out, ostride, M, K, 1, workspace,
-                          workspace_bytes, st);
-    if (rc > 0 && (rc = zero_side_job(*src, st)) == PN2_OK) rc = 1;
-    if (rc == 0)
-        rc = try_launch_dense_split(*src, layers, nlayers, pool, out, ostride, workspace,
-                                    workspace_bytes, M, K, 1, st);
-    if (rc < 0) return rc;
-    if (rc == 0)
-        return set_error(PN2_EUNSUPPORTED,
-                         "pn2_sa_mlp_max_bf16: no bf16 kernel for this chain (%d layers, mode %d) "
-                         "or workspace too small", nlayers, src->mode);
-    g_last_path = PN2_PATH_BF16;
-    g_last_planes = 1;
-    return PN2_OK;
-}
-
-// The entry points: the MLP, and the caller's FPS side job (pn2_fps_side) -- inside the chain
-// launch when try_launch_chain took it, else as its own launch after the MLP's
-template <typename F>
-static int with_fps_side(const pn2_sa_src *src, void *stream, F &&mlp) {
-    const pn2_fps_side *side = src ? src->fps_side : nullptr;
-    if (side) {
-        const int rc = fps_side_check(*side);
-        if (rc != PN2_OK) return rc;
-    }
-    fps_side_taken() = false;
-    const int rc = mlp();
-    const bool taken = fps_side_taken();
-    fps_side_taken() = false;
-    if (rc != PN2_OK) return rc;
-    g_last_side = !side ? -1 : taken ? 1 : 0;
-    if (!side || taken) return rc;
-    return fps_side_launch(*side, as_stream(stream));
-}
-
-extern "C" int pn2_sa_mlp_max_f32(const pn2_sa_src *src, const pn2_mlp_layer *layers,
-                                  int nlayers, int pool, float *out, int64_t ostride,
-                                  float *workspace, int64_t workspace_bytes, void *stream) {
-    return with_fps_side(src, stream, [&] {
-        return mlp_max_f32(src, layers, nlayers, pool, out, ostride, workspace, workspace_bytes, stream);
-    });
-}
-
-extern "C" int pn2_sa_mlp_max_bf16(const pn2_sa_src *src, const pn2_mlp_layer *layers,
-                                   int nlayers, int pool, float *out, int64_t ostride,
-                                   float *workspace, int64_t workspace_bytes, void *stream) {
-    return with_fps_side(src, stream, [&] {
-        return mlp_max_bf16(src, layers, nlayers, pool, out, ostride, workspace, workspace_bytes, stream);
-    });
+    r.path = PN2_PATH_F32;
+    r.planes = 0;
+    return 1;
 }

@@ -142,6 +142,65 @@ def test_workspace_query(widths, cin, mode, fused):
     assert (ws == 0) == fused and ws >= 0
 
 
+# (name, mode, cin, widths, split images, counts, tuning override) -> (f32 bytes, bf16 bytes), each
+# recorded once from the library before the host dispatch had one planner per kernel family
+# (default tuning; B = 2, N = 1024, S = 128, K = 32, group_all S = 1, K = 1024).
+WS_TABLE = [
+    ("ssg_sa1", 0, 3, [64, 64, 128], True, False, {}, (0, 0)),
+    ("ssg_sa1_cnt", 0, 3, [64, 64, 128], True, True, {}, (4608, 4608)),
+    ("ssg_sa2", 0, 131, [128, 128, 256], True, False, {}, (1179648, 0)),
+    ("ssg_sa2_cnt", 0, 131, [128, 128, 256], True, True, {}, (1184256, 4608)),
+    ("msg_sa2", 1, 323, [128, 128, 256], True, False, {}, (1179648, 0)),
+    ("group_all", 2, 259, [256, 512, 1024], True, False, {}, (8396800, 8396800)),
+    ("rows_wide", 3, 512, [1024], True, False, {}, (0, 0)),
+    ("rows_two", 3, 128, [256, 512], True, False, {}, (16793600, 16793600)),
+    ("f32_only", 0, 3, [96, 160, 128], False, False, {}, (10485760, 0)),
+    ("ssg_sa2_cnt_noprepass", 0, 131, [128, 128, 256], True, True, {"chain_prepass": 0}, (4608, 4608)),
+    ("ssg_sa2_cnt_nocompact", 0, 131, [128, 128, 256], True, True, {"compact": 0}, (1179648, 0)),
+    # the fp32 kernels run this chain fused (no workspace); the earlier query still asked for the
+    # chain kernel's pre-pass and compact bytes (PARENT_F32_OVERASK), which no launch under
+    # mlp_f32 = 1 used.  The bf16 entry ignores mlp_f32: its size is unchanged.
+    ("ssg_sa2_cnt_mlp_f32", 0, 131, [128, 128, 256], True, True, {"mlp_f32": 1}, (0, 4608)),
+]
+PARENT_F32_OVERASK = 1184256
+
+
+def ws_query(mode, cin, widths, split, cnt):
+    from pn2 import _lib
+    L = _lib.load()
+    s = _lib.SaSrc()
+    s.mode = mode
+    s.pts = s.ctr = s.idx = 16
+    s.B, s.N, s.C, s.S, s.K = 2, 1024, 3, 128, 32
+    if mode == 3:
+        s.rows, s.rs = 16, cin
+    else:
+        s.D = cin - 3
+        s.feat = 16 if s.D else None
+        s.fn, s.fb = s.D, 1024 * s.D
+    if mode == 2:
+        s.S, s.K = 1, 1024
+    if cnt:
+        s.cnt = 16
+    layers = _layers(widths, cin)
+    for q in layers:
+        q.wt_split = 16 if split else None
+    return (L.pn2_sa_mlp_workspace_bytes(s, layers, len(widths)),
+            L.pn2_sa_mlp_workspace_bytes_bf16(s, layers, len(widths)))
+
+
+@pytest.mark.parametrize("name,mode,cin,widths,split,cnt,keys,want", WS_TABLE, ids=[r[0] for r in WS_TABLE])
+def test_workspace_bytes_table(name, mode, cin, widths, split, cnt, keys, want):
+    """Both size queries return what the launches use: the sizes of the library before the
+    planner refactor, except where that one asked for bytes no launch would touch."""
+    from pn2 import tuning
+    with tuning.override(**keys):
+        got = ws_query(mode, cin, widths, split, cnt)
+    assert got == want
+    if keys.get("mlp_f32"):
+        assert PARENT_F32_OVERASK > got[0]
+
+
 def test_io_library_exports_every_declared_symbol():
     """libpn2io.so (the dataset text reader, host code) against include/pn2io.h."""
     from pn2 import data

@@ -566,3 +566,59 @@ def test_chain_ragged_rows_batch_independent(case, compact):
         ratio = float((np.abs(gotn[b] - want[b]) / tol).max())
         print("case %d compact %d cloud %d: max err / tol %.4f" % (case, compact, b, ratio))
         assert ratio < 0.1
+
+
+def test_report_is_per_call():
+    """pn2_sa_mlp_last_path / _planes / _fps_side describe the thread's last successful call,
+    whichever kernel family ran it: nothing of an earlier call's report leaks into the next, and
+    a call that fails validation leaves the report alone."""
+    import pn2
+    from pn2 import _lib, ops
+    from pn2.pointnet2_utils import _pack_chain
+    L = _lib.load()
+
+    def report():
+        return L.pn2_sa_mlp_last_path(), L.pn2_sa_mlp_last_planes(), L.pn2_sa_mlp_last_fps_side()
+
+    torch.manual_seed(4)
+    sa = pn2.PointNetSetAbstraction(16, 16, 0.4, 3, [64, 64, 128])
+    cases.randomize_bn(sa, 4)
+    sa = sa.to(DEV).eval()
+    B, N, S, K = 2, 64, 16, 16
+    pts = cases.cloud("uniform3", B, N, 7).to(DEV)
+    with torch.no_grad():
+        s0 = torch.randint(0, N, (B,), generator=torch.Generator().manual_seed(1))
+        _, newp, cpk, ppk = ops.fps_direct(pts, S, s0)
+        idx, cnt = ops.ball_query_direct(ppk, cpk, 3, 0.4, K, True)
+        wts, als, bes, cins, splits = _pack_chain(sa.mlp_convs, sa.mlp_bns, sa._pack_cache, 0, 3, True)
+        ref = torch.empty(B * S, 128, device=DEV)
+        ops.sa_mlp_max_impl(ref, 0, pts, None, newp, idx, wts, als, bes, cins, splits, cnt=cnt)
+        # (a) the chain with an FPS side job that fits its launch
+        st = torch.randint(0, S, (B,), generator=torch.Generator().manual_seed(2))
+        job, outs = ops.fps_side_job(newp, 8, st)
+        out = torch.empty_like(ref)
+        ops.sa_mlp_max_impl(out, 0, pts, None, newp, idx, wts, als, bes, cins, splits, cnt=cnt, fps_side=job)
+        a = report()
+        assert (a[0], a[2]) == (_lib.PATH_SPLIT_BF16, 1)
+        assert torch.equal(out, ref)
+        assert torch.equal(outs[0], ops.fps_direct(newp, 8, st)[0])
+        # (b) group_all on a tiny cloud: the dense layers, no side job
+        ga = pn2.PointNetSetAbstraction(None, None, None, 3 + 13, [64, 96], True)
+        cases.randomize_bn(ga, 5)
+        ga = ga.to(DEV).eval()
+        feat = torch.randn(B, 13, 32, generator=torch.Generator().manual_seed(6)).to(DEV)
+        ga(cases.cloud("uniform3", B, 32, 8).permute(0, 2, 1).contiguous().to(DEV), feat)
+        b = report()
+        assert (b[0], b[2]) == (_lib.PATH_SPLIT_BF16, -1)
+        # (c) no split images: the fp32 kernels
+        ops.sa_mlp_max_impl(out, 0, pts, None, newp, idx, wts, als, bes, cins, [], cnt=cnt)
+        assert report() == (_lib.PATH_F32, 0, -1)
+        # (d) a call that fails validation (output rows narrower than the last layer)
+        with pytest.raises(RuntimeError, match="ostride"):
+            ops.sa_mlp_max_impl(torch.empty(B * S, 64, device=DEV), 0, pts, None, newp, idx, wts, als, bes,
+                                cins, splits, cnt=cnt, fps_side=job)
+        assert report() == (_lib.PATH_F32, 0, -1)
+        # (e) the bf16 entry on (a)'s shape
+        ops.sa_mlp_max_impl(out, 0, pts, None, newp, idx, wts, als, bes, cins, splits, precision="bf16", cnt=cnt)
+        assert report() == (_lib.PATH_BF16, 1, -1)
+    torch.cuda.synchronize()
