@@ -47,6 +47,10 @@
  *                          + provider.splice_torch + transpose (+ the translation heads' mean)
  *                                                            provider.py:5-21, 166-180;
  *                                                            test_translation.py:72-79
+ *   pn2_prepare_train_points_f64  the same after the training scripts' augmentations
+ *                          (random_point_dropout, random_scale_point_cloud, shift_point_cloud)
+ *                                                            provider.py:131-164;
+ *                                                            train_translation.py:109-119
  */
 #ifndef PN2_H
 #define PN2_H
@@ -62,7 +66,7 @@ extern "C" {
 #define PN2_EUNSUPPORTED (-2) /* shape outside what the kernels are built for */
 #define PN2_EHIP (-3)       /* HIP runtime error at launch */
 
-#define PN2_ABI_VERSION 17
+#define PN2_ABI_VERSION 18
 
 int pn2_abi_version(void);
 const char *pn2_last_error(void);
@@ -341,6 +345,23 @@ int pn2_sa_mlp_max_bf16(const pn2_sa_src *src, const pn2_mlp_layer *layers, int 
 int pn2_prepare_points_f64(const double *pts, int64_t B, int64_t N, int64_t C, int64_t sb,
                            int64_t sn, int64_t sc, int normalize, const int64_t *labels,
                            int64_t num_category, float *out, float *mean_out, void *stream);
+/* The training scripts' preparation (train_translation.py:109-119; train_rotation.py:108-116
+ * without the mean): pn2_prepare_points_f64 on the batch the augmentations leave, with the
+ * draws made by the caller (pn2.provider.draw_augmentation consumes numpy's generator as the
+ * reference does).  The value of point n, channel c that everything above consumes is
+ *   p = pts[b, drop[b*N + n] ? 0 : n, c]            random_point_dropout (provider.py:157-164):
+ *                                                   a dropped row is row 0's, all C channels
+ *   c < 3:  p = fl(fl(p * scale[b]) + shift[b*3 + c])   random_scale_point_cloud, then
+ *                                                   shift_point_cloud: two roundings, no FMA
+ *   c >= 3: p unchanged
+ * so mean_out is the mean of the first min(3,N) AUGMENTED points, and the centroid, the max
+ * norm and the divide see the augmented cloud.  drop: uint8 [B,N] (non-zero = dropped), scale:
+ * float64 [B], shift: float64 [B,3]; device pointers, each NULL to skip that stage (all three
+ * NULL computes exactly pn2_prepare_points_f64).  pts is not written. */
+int pn2_prepare_train_points_f64(const double *pts, int64_t B, int64_t N, int64_t C, int64_t sb,
+                                 int64_t sn, int64_t sc, int normalize, const int64_t *labels,
+                                 int64_t num_category, const uint8_t *drop, const double *scale,
+                                 const double *shift, float *out, float *mean_out, void *stream);
 
 /* ---- training (batch-statistics BatchNorm) around library GEMMs; rows are channels-last
  * [M][C] with row stride ld.  Workspace: pn2_bn_train_workspace_bytes(M, C) bytes (float64

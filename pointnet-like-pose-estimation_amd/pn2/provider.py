@@ -15,7 +15,22 @@ operation order, one rounding to float32) and the same ``mean``, computed on the
 the float64 batch (host or device tensor, or numpy array).  The points come back as the
 reference's [B, C+K, N] view of [B, N, C+K] storage -- the layout its models receive, which
 the SA path's FPS / ball-query sum orders depend on.
+
+The training loops (train_translation.py:109-119; train_rotation.py:108-116 and
+train_sign.py:107-115 without the mean; train_classification.py:107-112 without the splice)
+augment the batch first, on the host, in place:
+
+    points = provider.random_point_dropout(points)                            # per-cloud loop
+    points[:, :, 0:3] = provider.random_scale_point_cloud(points[:, :, 0:3])  # per-cloud loop
+    points[:, :, 0:3] = provider.shift_point_cloud(points[:, :, 0:3])         # per-cloud loop
+
+``prepare_train_batch`` is that whole sequence as one launch: ``draw_augmentation`` makes the
+random draws on the host, consuming numpy's generator exactly as the three functions do, and
+the kernel applies them while it reads the batch.  For the same generator state the model
+input and the mean are the reference's, bit for bit.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -23,28 +38,24 @@ from . import _lib
 from .ops import _stream
 
 
-def prepare_batch(points, label=None, num_category=7, with_mean=False, normalize=True,
-                  device=None):
-    """points: float64 [B, N, C] (torch tensor on any device, or numpy), C >= 3.
-    label: [B] class indices (one-hot spliced after the C channels when given; values must be
-    in [0, num_category) -- the reference raises IndexError otherwise).
-    Returns (model input [B, C+K, N] float32 on the device, mean [B, C] float32 or None)."""
+def _check_batch(who, points, label, num_category, normalize):
+    """The input rules both entries share -> (points tensor, int64 labels or None, K)."""
     if isinstance(points, np.ndarray):
         points = torch.from_numpy(points)
     if points.dtype != torch.float64:
-        raise TypeError("pn2.provider.prepare_batch: points must be float64 (np.loadtxt rows), "
-                        "got %s" % points.dtype)
+        raise TypeError("pn2.provider.%s: points must be float64 (np.loadtxt rows), "
+                        "got %s" % (who, points.dtype))
     if points.dim() != 3:
-        raise ValueError("pn2.provider.prepare_batch: points must be [B, N, C]")
+        raise ValueError("pn2.provider.%s: points must be [B, N, C]" % who)
     B, N, C = points.shape
     if normalize and C < 3:
-        raise ValueError("pn2.provider.prepare_batch: normalising needs C >= 3")
+        raise ValueError("pn2.provider.%s: normalising needs C >= 3" % who)
     K = 0
     lab = None
     if label is not None:
         lab = torch.as_tensor(label).reshape(-1).to(torch.int64)
         if lab.numel() != B:
-            raise ValueError("pn2.provider.prepare_batch: %d labels for %d clouds" % (lab.numel(), B))
+            raise ValueError("pn2.provider.%s: %d labels for %d clouds" % (who, lab.numel(), B))
         # host labels (the DataLoader's) are range-checked like the reference; device labels
         # are not (that would synchronise): an out-of-range one gets an all-zero one-hot
         lab_host = lab if not lab.is_cuda else None
@@ -53,6 +64,10 @@ def prepare_batch(points, label=None, num_category=7, with_mean=False, normalize
                 int(lab_host.max()) if int(lab_host.max()) >= num_category else int(lab_host.min()),
                 num_category))
         K = int(num_category)
+    return points, lab, K
+
+
+def _pick_device(who, points, device):
     if device is not None:
         dev = torch.device(device)
     elif points.is_cuda:
@@ -62,8 +77,20 @@ def prepare_batch(points, label=None, num_category=7, with_mean=False, normalize
     else:
         dev = torch.device("cpu")
     if dev.type != "cuda":
-        raise RuntimeError("pn2.provider.prepare_batch: runs on ROCm devices only (got %s); "
-                           "there is no CPU path" % dev)
+        raise RuntimeError("pn2.provider.%s: runs on ROCm devices only (got %s); "
+                           "there is no CPU path" % (who, dev))
+    return dev
+
+
+def prepare_batch(points, label=None, num_category=7, with_mean=False, normalize=True,
+                  device=None):
+    """points: float64 [B, N, C] (torch tensor on any device, or numpy), C >= 3.
+    label: [B] class indices (one-hot spliced after the C channels when given; values must be
+    in [0, num_category) -- the reference raises IndexError otherwise).
+    Returns (model input [B, C+K, N] float32 on the device, mean [B, C] float32 or None)."""
+    points, lab, K = _check_batch("prepare_batch", points, label, num_category, normalize)
+    B, N, C = points.shape
+    dev = _pick_device("prepare_batch", points, device)
     if lab is not None:
         lab = lab.to(dev, non_blocking=True)
     pts = points.to(dev, non_blocking=True)
@@ -78,4 +105,103 @@ def prepare_batch(points, label=None, num_category=7, with_mean=False, normalize
     return out.transpose(2, 1), mean
 
 
-__all__ = ["prepare_batch"]
+# One batch's random draws.  drop: bool [B, N] (True = the point is replaced by point 0),
+# scale: float64 [B], shift: float64 [B, 3]; None = that augmentation is off.
+Augmentation = collections.namedtuple("Augmentation", ["drop", "scale", "shift"])
+
+
+def draw_augmentation(B, N, dropout=True, scale=True, shift=True, max_dropout_ratio=0.875,
+                      scale_low=0.8, scale_high=1.25, shift_range=0.1, rng=None):
+    """The draws of random_point_dropout, random_scale_point_cloud and shift_point_cloud
+    (provider.py:157-164, 144-155, 131-142) for a [B, N, .] batch, from the global np.random
+    (rng=None) or an np.random.RandomState, consumed exactly as those functions consume it:
+      1. per cloud, random() then random(N);  drop = u <= random() * max_dropout_ratio
+         (float64 comparison).  Drawn as one random((B, N + 1)): the same doubles in the same
+         order, and the same generator state afterwards
+      2. uniform(scale_low, scale_high, B)
+      3. uniform(-shift_range, shift_range, (B, 3))
+    A stage switched off draws nothing and is None in the result."""
+    rs = np.random if rng is None else rng
+    drop = sc = sh = None
+    if dropout:
+        u = rs.random_sample((B, N + 1))
+        drop = u[:, 1:] <= u[:, :1] * max_dropout_ratio
+    if scale:
+        sc = rs.uniform(scale_low, scale_high, B)
+    if shift:
+        sh = rs.uniform(-shift_range, shift_range, (B, 3))
+    return Augmentation(drop, sc, sh)
+
+
+def _check_augmentation(aug, B, N):
+    """-> (drop uint8 [B,N], scale f64 [B], shift f64 [B,3]) host arrays, None where off."""
+    parts = []
+    for name, dtype, shape in (("drop", np.bool_, (B, N)), ("scale", np.float64, (B,)),
+                               ("shift", np.float64, (B, 3))):
+        v = getattr(aug, name)
+        if v is not None:
+            v = np.asarray(v)
+            if v.shape != shape:
+                raise ValueError("pn2.provider.prepare_train_batch: aug.%s has shape %s, the "
+                                 "batch needs %s" % (name, tuple(v.shape), shape))
+            v = np.ascontiguousarray(v, dtype=dtype)
+        parts.append(v)
+    return parts
+
+
+def prepare_train_batch(points, label=None, num_category=7, with_mean=False, normalize=True,
+                        aug=None, device=None, **draw_kwargs):
+    """prepare_batch after the training scripts' augmentations (train_translation.py:109-119),
+    in one launch.  points / label / num_category / with_mean / normalize / device and the
+    errors are prepare_batch's.
+
+    aug: an Augmentation to use as it is (shape-checked; a caller can draw the next batch's
+    while the GPU works), or None to call draw_augmentation(B, N, **draw_kwargs) here.  The
+    draws reach the device in one non-blocking copy from pinned memory on the kernel's stream.
+
+    The reference augments its numpy batch in place; this never writes to `points` -- the
+    augmented float64 batch exists only inside the kernel.
+    Returns (model input [B, C+K, N] float32 on the device, mean [B, C] float32 or None); the
+    mean is of the first 3 augmented points, as train_translation.py:113 takes it."""
+    who = "prepare_train_batch"
+    points, lab, K = _check_batch(who, points, label, num_category, normalize)
+    B, N, C = points.shape
+    if aug is not None:
+        if draw_kwargs:
+            raise TypeError("pn2.provider.prepare_train_batch: draw options %s given with an "
+                            "explicit aug" % sorted(draw_kwargs))
+        parts = _check_augmentation(aug, B, N)
+    dev = _pick_device(who, points, device)
+    if aug is None:
+        parts = _check_augmentation(draw_augmentation(B, N, **draw_kwargs), B, N)
+    if lab is not None:
+        lab = lab.to(dev, non_blocking=True)
+    pts = points.to(dev, non_blocking=True)
+    out = torch.empty(B, N, C + K, dtype=torch.float32, device=dev)
+    mean = torch.empty(B, C, dtype=torch.float32, device=dev) if with_mean else None
+    if B and N:
+        # one pinned staging buffer [scale | shift | drop] (the float64 parts first: aligned)
+        drop, sc, sh = parts
+        blobs = [v.reshape(-1).view(np.uint8) for v in (sc, sh, drop) if v is not None]
+        ptr = {}
+        if blobs:
+            total = sum(v.size for v in blobs)
+            stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            np.concatenate(blobs, out=stage.numpy())
+            with torch.cuda.device(dev):
+                d_stage = stage.to(dev, non_blocking=True)
+            off = 0
+            for name, v in (("scale", sc), ("shift", sh), ("drop", drop)):
+                if v is not None:
+                    ptr[name] = d_stage.data_ptr() + off
+                    off += v.nbytes
+        L = _lib.load()
+        _lib.check(L.pn2_prepare_train_points_f64(
+            pts.data_ptr(), B, N, C, pts.stride(0), pts.stride(1), pts.stride(2),
+            1 if normalize else 0, 0 if lab is None else lab.data_ptr(), K,
+            ptr.get("drop", 0), ptr.get("scale", 0), ptr.get("shift", 0), out.data_ptr(),
+            0 if mean is None else mean.data_ptr(), _stream(out)), "pn2_prepare_train_points_f64")
+    return out.transpose(2, 1), mean
+
+
+__all__ = ["prepare_batch", "prepare_train_batch", "draw_augmentation", "Augmentation"]
