@@ -390,7 +390,7 @@ int pn2_group_max_f32(const float *A, int64_t G, int64_t K, int64_t C, int64_t l
 /* Backward of A = relu(bn_train(Y)): dXn = dA * [A > 0] (dA with flags PN2_LAYER_NO_RELU, the
  * backward of A = bn_train(Y)), with dA dense (ldd) or, when dA is
  * NULL, scattered from the max: dA[r][c] = dOut[r/K][c] if arg[r/K][c] == r%K else 0.
- * dbeta = sum_r dXn, dgamma = sum_r dXn*xhat (float64 sums), and
+ * dbeta = sum_r dXn, dgamma = sum_r dXn*xhat (float64 sums, of float64 products), and
  * dY = gamma*invstd*(dXn - dbeta/M - xhat*dgamma/M); dbias (or NULL) = sum_r dY, the preceding
  * conv's bias gradient, from the forward's sxhat. */
 int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, int64_t ld, const float *mean,

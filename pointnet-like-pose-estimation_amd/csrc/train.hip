@@ -19,7 +19,8 @@
 //   pn2_bn_relu_backward_f32  dXn = dA * [A > 0] (unmasked with PN2_LAYER_NO_RELU; dA from the
 //                             next layer, or scattered from the max: arg[g][c] == k ?
 //                             dOut[g][c] : 0), its column sums
-//                             S1 = sum dXn and S2 = sum dXn * xhat (= dbeta, dgamma), then
+//                             S1 = sum dXn and S2 = sum dXn * xhat (= dbeta, dgamma; float64
+//                             sums, xhat in float64 inside S2), then
 //                             dY = gamma * invstd * (dXn - S1/M - xhat * S2/M)
 // Layout: channels-last rows [M][C] with row stride ld (the SA path's layout), so every pass is
 // a coalesced column-tiled sweep: a 256-thread block covers 64 columns x 4 row lanes of one row
@@ -36,6 +37,13 @@ constexpr int kTrMinBlocks = 2048;  // column sweeps: enough blocks to fill 256 
 constexpr int kTrUnroll = 8;    // rows in flight per thread in the column sweeps
 
 __device__ __forceinline__ float tr_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
+// xhat for the dgamma sum.  The float32 one is off by up to 2 ulp per row, which the sum over M
+// rows does not average below S2's own size: S2 is a sum of signed terms, about sqrt(M) of them
+// in magnitude, so S2/M in dY lost digits on columns where it came out small (caught by
+// tests/test_gpu_train_kernels.py at C = 2048, M = 8197: 7x the float32 bound of dY).
+__device__ __forceinline__ double tr_xhat64(float y, float mean, float invstd) {
+    return ((double)y - (double)mean) * (double)invstd;
+}
 
 // partial column sums of Y and Y^2 over row chunk blockIdx.y -> part[chunk][2][C] (double)
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float *__restrict__ Y, int64_t M,
@@ -173,6 +181,17 @@ __device__ __forceinline__ bool tr_better(float v, int32_t a, float m, int32_t b
     return v > m || (v == m && a < b);
 }
 
+// One row of a lane's walk in increasing row order: strict > keeps the first maximum, a NaN
+// replaces a number only, the lane's first row replaces the start value.  Written as selects on
+// one flag: as a branch around the two assignments, the last row of the unrolled round came out
+// of the compiler updating m but not a when v was NaN (ROCm 7 clang, read in the ISA; caught by
+// tests/test_gpu_train_kernels.py test_group_max with a NaN on row 121 of K = 257).
+__device__ __forceinline__ void tr_take(float v, int32_t i, float &m, int32_t &a) {
+    const bool t = (v > m) | ((v != v) & (m == m)) | (a == 0x7fffffff);
+    m = t ? v : m;
+    a = t ? i : a;
+}
+
 // Large K (a PointNet-v1 max over a cloud's N points): one block per (group, 64 columns), the K
 // rows split over kTrWideLanes row lanes (8 rows in flight each), lanes merged through LDS.
 // One thread per (group, column) walking all K rows would serialise K/8 dependent load rounds.
@@ -197,14 +216,9 @@ __global__ __launch_bounds__(kTrCols * kTrWideLanes) void group_max_wide_kernel(
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[u] = p[(k + u * kTrWideLanes) * lda];
 #pragma unroll
-            for (int u = 0; u < 8; ++u)  // increasing row order within the lane: strict > keeps the first
-                if (v[u] > m || (v[u] != v[u] && m == m) || a == 0x7fffffff)
-                    m = v[u], a = (int32_t)(k + u * kTrWideLanes);
+            for (int u = 0; u < 8; ++u) tr_take(v[u], (int32_t)(k + u * kTrWideLanes), m, a);
         }
-        for (; k < K; k += kTrWideLanes) {
-            const float v = p[k * lda];
-            if (v > m || (v != v && m == m) || a == 0x7fffffff) m = v, a = (int32_t)k;
-        }
+        for (; k < K; k += kTrWideLanes) tr_take(p[k * lda], (int32_t)k, m, a);
     }
     sv[ty][tx] = m;
     sa[ty][tx] = a;
@@ -223,9 +237,10 @@ __device__ __forceinline__ float tr_dxn(const float *__restrict__ Y, int64_t ld,
                                         const float *__restrict__ dA, int64_t ldd,
                                         const float *__restrict__ dOut, int64_t ldo,
                                         const int32_t *__restrict__ arg, int64_t K, int64_t C,
-                                        int relu, float &xhat) {
+                                        int relu, float &y, float &xhat) {
     // branch-free: every load is issued whatever the ReLU mask, so unrolled rows stay in flight
-    xhat = tr_xhat(Y[r * ld + c], mean, invstd);
+    y = Y[r * ld + c];
+    xhat = tr_xhat(y, mean, invstd);
     float d;
     if (dA) {
         d = dA[r * ldd + c];
@@ -253,18 +268,18 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(
         const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
         int64_t r = r0 + ty;
         for (; r + (kTrUnroll - 1) * kTrLanes < r1; r += kTrUnroll * kTrLanes) {
-            float d[kTrUnroll], xh[kTrUnroll];
+            float d[kTrUnroll], y[kTrUnroll], xh;
 #pragma unroll
             for (int u = 0; u < kTrUnroll; ++u)
-                d[u] = tr_dxn(Y, ld, r + u * kTrLanes, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, xh[u]);
+                d[u] = tr_dxn(Y, ld, r + u * kTrLanes, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y[u], xh);
 #pragma unroll
-            for (int u = 0; u < kTrUnroll; ++u) s1 += (double)d[u], s2 += (double)d[u] * (double)xh[u];
+            for (int u = 0; u < kTrUnroll; ++u) s1 += (double)d[u], s2 += (double)d[u] * tr_xhat64(y[u], mu, is);
         }
         for (; r < r1; r += kTrLanes) {
-            float xh;
-            const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, xh);
+            float y, xh;
+            const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y, xh);
             s1 += (double)d;
-            s2 += (double)d * (double)xh;
+            s2 += (double)d * tr_xhat64(y, mu, is);
         }
     }
     red[0][ty][tx] = s1;
@@ -297,10 +312,11 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_gather_kernel(
         const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
         for (int64_t g = g0 + ty; g < g1; g += kTrLanes) {
             const int64_t r = g * K + arg[g * C + c];
-            const float xh = tr_xhat(Y[r * ld + c], mu, is);
+            const float y = Y[r * ld + c];
+            const float xh = tr_xhat(y, mu, is);
             const float d = !relu || xh * ga + be > 0.f ? dOut[g * ldo + c] : 0.f;
             s1 += (double)d;
-            s2 += (double)d * (double)xh;
+            s2 += (double)d * tr_xhat64(y, mu, is);
         }
     }
     red[0][ty][tx] = s1;
@@ -345,8 +361,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const int64_t r1 = r0 + kTrEwRows < M ? r0 + kTrEwRows : M;
 #pragma unroll 4
     for (int64_t r = r0 + ty; r < r1; r += kTrLanes) {
-        float xh;
-        const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, xh);
+        float y, xh;
+        const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y, xh);
         dY[r * ldy + c] = ga * is * (d - m1 - xh * m2);
     }
 }
@@ -390,7 +406,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_vec_kernel(
                     const float xh = tr_xhat(yv[j], mus[j], iss[j]);
                     const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
                     s1[j] += (double)dd;
-                    s2[j] += (double)dd * (double)xh;
+                    s2[j] += (double)dd * tr_xhat64(yv[j], mus[j], iss[j]);
                 }
             }
         }
@@ -402,7 +418,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_vec_kernel(
                 const float xh = tr_xhat(yv[j], mus[j], iss[j]);
                 const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
                 s1[j] += (double)dd;
-                s2[j] += (double)dd * (double)xh;
+                s2[j] += (double)dd * tr_xhat64(yv[j], mus[j], iss[j]);
             }
         }
     }
@@ -592,9 +608,13 @@ extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, in
                            relu, chunk_rows(M, C), part);
         PN2_LAUNCH_CHECK("bn_bwd_partial_kernel");
     } else {  // scattered from the max: only the G argmax rows contribute
-        const int64_t G = M / K, gch = chunk_rows(G, C);
+        // The workspace holds chunks(M, C) partials.  chunk_rows(G, C) halves from another start
+        // than chunk_rows(M, C), so with K no power of two G/gch can pass M/ch (C=4, K=3,
+        // G=174678: 2730 against 2048); the group chunk is then doubled until it fits.
+        const int64_t G = M / K, cap = chunks(M, C);
+        int64_t gch = chunk_rows(G, C);
+        while ((G + gch - 1) / gch > cap) gch <<= 1;
         nch = (G + gch - 1) / gch;
-        PN2_REQUIRE(nch <= chunks(M, C), "pn2_bn_relu_backward_f32: gather partials exceed the workspace");
         hipLaunchKernelGGL(bn_bwd_partial_gather_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)nch),
                            dim3(256), 0, st, Y, G, C, ld, mean, invstd, gamma, beta, dOut, ldo, arg, K, relu, gch,
                            part);

@@ -262,3 +262,91 @@ def test_trainv1_step_matches_reference(name):
         train.point_mlp_train = orig
     assert calls, "the fused training kernels did not run"
     _v1_check(model, g, outs, 1e-4, 2e-3, pre="t.")
+
+
+# ------------------------------------------------------------------ against torch float64 (CPU)
+# name -> (kind, Cin, couts, K, M, BatchNorm keywords, steps).  kind "max": mlp_max_train on
+# [1, M/K, K, Cin] groups; "rows": point_mlp_train on [3, M/3, Cin] rows without the max.
+F64_CASES = {
+    # channel counts that are no multiple of 4: the unvectorised backward kernels
+    "scalar_kernels": ("max", 6, [30, 7], 20, 60 * 20, {}, 1),
+    "dense_rows": ("rows", 4, [5], 0, 3 * 50, {}, 1),
+    # _grad_weight: four 2048-row chunks through bmm and a 300-row tail through mm
+    # (K = 44 = 8492 / 193: with a small K many groups are all zero after the ReLU, exact ties)
+    "grad_weight_tail": ("max", 3, [64], 44, 4 * 2048 + 300, {}, 1),
+    # momentum None: cumulative average, factor 1/1 then 1/2
+    "cumulative_average": ("max", 6, [16], 8, 40 * 8, {"momentum": None}, 2),
+    # no running statistics at all: null pointers, momentum 0
+    "no_running_stats": ("max", 6, [16], 8, 40 * 8, {"track_running_stats": False}, 1),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(F64_CASES))
+def test_train_mlp_matches_torch_float64(name):
+    """mlp_max_train / point_mlp_train against the same layers run by torch on the CPU in
+    float64: outputs and running statistics 1e-4, gradients 1e-3 (close's relative bound plus
+    max-scaled floor).  Near-ties of a group's two largest values are taken out as in
+    test_train_mlp_matches_torch_on_device, at most 1% of the (group, channel) pairs."""
+    import copy
+    from pn2 import train
+    kind, cin, couts, K, M, bn_kw, steps = F64_CASES[name]
+    torch.manual_seed(M + len(name))
+    dims = [cin] + couts
+    conv_t, bn_t = ((torch.nn.Conv2d, torch.nn.BatchNorm2d) if kind == "max"
+                    else (torch.nn.Conv1d, torch.nn.BatchNorm1d))
+    convs = [conv_t(dims[i], dims[i + 1], 1) for i in range(len(couts))]
+    bns = [bn_t(c, **bn_kw) for c in couts]
+    with torch.no_grad():
+        for bn in bns:
+            bn.weight.copy_(torch.rand(bn.num_features) + 0.5)
+            bn.bias.copy_(torch.rand(bn.num_features) * 0.2 - 0.1)
+            if bn.running_mean is not None:
+                bn.running_mean.copy_(torch.rand(bn.num_features) * 0.2 - 0.1)
+                bn.running_var.copy_(torch.rand(bn.num_features) + 0.5)
+    ref = [copy.deepcopy(m).double().train() for m in convs + bns]
+    dev = [m.cuda().train() for m in convs + bns]
+    n = len(couts)
+    for step in range(steps):
+        x = torch.randn(1, M // K, K, cin) if kind == "max" else torch.randn(3, M // 3, cin)
+        xa = x.cuda().requires_grad_(True)
+        xb = x.double().requires_grad_(True)
+        for m in ref + dev:
+            m.zero_grad()
+        assert train.eligible(xa, dev[:n], dev[n:])
+        if kind == "max":
+            out_a = train.mlp_max_train(xa, dev[:n], dev[n:])
+            h = xb.permute(0, 3, 2, 1)
+        else:
+            out_a = train.point_mlp_train(xa, dev[:n], dev[n:], True, pool=False)
+            h = xb.permute(0, 2, 1)
+        for c, b in zip(ref[:n], ref[n:]):
+            h = torch.relu(b(c(h)))
+        if kind == "max":
+            out_b = torch.max(h, 2)[0]
+            top2 = torch.topk(h, 2, dim=2)[0]
+            clear = (top2[:, :, 0] - top2[:, :, 1]) > 1e-4 * (top2[:, :, 0].abs() + 1e-2)
+        else:
+            out_b = h.permute(0, 2, 1)
+            clear = torch.ones_like(out_b, dtype=torch.bool)
+        assert float((~clear).sum()) <= 0.01 * clear.numel(), "near-ties: %d of %d" % ((~clear).sum(), clear.numel())
+        R = torch.randn(out_b.shape) * clear
+        (out_a * R.cuda()).sum().backward()
+        (out_b * R.double()).sum().backward()
+        close(out_a.detach().cpu(), out_b.detach(), 1e-4, "out")
+        close(xa.grad.cpu(), xb.grad, 1e-3, "dx")
+        for a, b in zip(dev, ref):
+            for (k, p), (_, q) in zip(a.named_parameters(), b.named_parameters()):
+                if k == "bias" and not isinstance(a, bn_t):  # ~0: see above
+                    scale = float(b.weight.grad.abs().max())
+                    assert float(p.grad.abs().max()) <= 1e-4 * scale
+                    assert float(q.grad.abs().max()) <= 1e-4 * scale
+                    continue
+                close(p.grad.cpu(), q.grad, 1e-3, "step %d grad %s" % (step, k))
+            bufs_a, bufs_b = dict(a.named_buffers()), dict(b.named_buffers())
+            assert sorted(bufs_a) == sorted(bufs_b)
+            for k in bufs_a:
+                if k == "num_batches_tracked":
+                    assert int(bufs_a[k]) == int(bufs_b[k]) == step + 1
+                else:
+                    close(bufs_a[k].cpu(), bufs_b[k], 1e-4, "step %d %s" % (step, k))
