@@ -39,7 +39,11 @@
  *                                                            (under autograd: train_rotation.py:99-133)
  *                          and the v1 shared MLPs' Conv1d + BatchNorm1d (+ ReLU) + max over N
  *                                                            model/pointnet_utils.py:31-35, 118-128
- *   pn2_linear_rows_f32    eval Linear + BatchNorm1d (folded on the host) + ReLU of the FC tails
+ *   pn2_bn_relu_group_max_f32 / pn2_bn_relu_backward_f32 with PN2_LAYER_FROZEN_STATS
+ *                          eval-mode BatchNorm2d + ReLU + torch.max over K under autograd
+ *                                                            model/pointnet2_utils.py:163-172, 211-221
+ *                                                            (mutilthreading/predict_test.py:25-63)
+ *   pn2_linear_rows_f32   eval Linear + BatchNorm1d (folded on the host) + ReLU of the FC tails
  *                                                            model/pointnet_utils.py:33-40;
  *                                                            pointnet_cls.py:26-28; rotation.py:45-49;
  *                                                            pointnet2_cls_ssg.py:32-34
@@ -66,7 +70,7 @@ extern "C" {
 #define PN2_EUNSUPPORTED (-2) /* shape outside what the kernels are built for */
 #define PN2_EHIP (-3)       /* HIP runtime error at launch */
 
-#define PN2_ABI_VERSION 18
+#define PN2_ABI_VERSION 19
 
 int pn2_abi_version(void);
 const char *pn2_last_error(void);
@@ -240,6 +244,9 @@ typedef struct pn2_mlp_layer {
  * training entry points (pn2_bn_relu_apply_f32 / pn2_bn_relu_backward_f32) take it as their
  * flags argument. */
 #define PN2_LAYER_NO_RELU 1
+/* pn2_bn_relu_backward_f32 only: mean / invstd are the caller's running statistics (eval-mode,
+ * "frozen" BatchNorm), constants of the backward. */
+#define PN2_LAYER_FROZEN_STATS 2
 
 /* The same W packed for the split chain / dense kernels.  Planes 0-2: three bf16 planes (hi, mid,
  * lo with W = hi + mid + lo to 2^-24 relative), each [cout/32][kblocks][64 lanes][8] in MFMA
@@ -399,6 +406,18 @@ int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, int64_t ld, c
                              const int32_t *arg, int64_t K, const double *sxhat, float *dY,
                              int64_t ldy, float *dgamma, float *dbeta, float *dbias, void *ws,
                              int64_t ws_bytes, int flags, void *stream);
+/* With flags PN2_LAYER_FROZEN_STATS the same entry is the backward of A = relu(bn_eval(Y)):
+ * mean / invstd are running statistics, dXn, dbeta and dgamma as above,
+ * dY = gamma*invstd*dXn (no batch-statistics correction), dbias = gamma*invstd*dbeta; sxhat is
+ * not read and may be NULL. */
+/* pn2_bn_relu_apply_f32 followed by pn2_group_max_f32 in one pass over Y, without writing A:
+ * out[g*ldo + c] = max over k < K of act((Y[(g*K + k)*ld + c] - mean)*invstd*gamma + beta),
+ * arg[g*C + c] = its first argmax (int32), NaN the maximum; out and arg are bit-identical to the
+ * two calls.  flags: PN2_LAYER_NO_RELU. */
+int pn2_bn_relu_group_max_f32(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld,
+                              const float *mean, const float *invstd, const float *gamma,
+                              const float *beta, float *out, int64_t ldo, int32_t *arg, int flags,
+                              void *stream);
 
 /* ---- small-batch fully connected layer (the eval FC tails, BN folded into W / bias on the
  * host): out[b*ldo + n] = act(sum_k x[b*ldx + k] * W[n*K + k] + bias[n]) for b < B (rows in

@@ -21,7 +21,11 @@
 //                             dOut[g][c] : 0), its column sums
 //                             S1 = sum dXn and S2 = sum dXn * xhat (= dbeta, dgamma; float64
 //                             sums, xhat in float64 inside S2), then
-//                             dY = gamma * invstd * (dXn - S1/M - xhat * S2/M)
+//                             dY = gamma * invstd * (dXn - S1/M - xhat * S2/M); with
+//                             PN2_LAYER_FROZEN_STATS (mean / invstd are running statistics, the
+//                             eval-mode BatchNorm) dY = gamma * invstd * dXn
+//   pn2_bn_relu_group_max_f32 apply + group max in one pass over Y, A never written (the pooled
+//                             last layer of the frozen-statistics recompute, pn2/train.py)
 // Layout: channels-last rows [M][C] with row stride ld (the SA path's layout), so every pass is
 // a coalesced column-tiled sweep: a 256-thread block covers 64 columns x 4 row lanes of one row
 // chunk and reduces through LDS; chunk partials are merged in float64 by a per-column pass.
@@ -329,6 +333,9 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_gather_kernel(
     }
 }
 
+// FROZEN (PN2_LAYER_FROZEN_STATS): mean / invstd are constants of the caller (running statistics),
+// so dY carries no batch-statistics correction and sum_r dY = gamma*invstd*S1; sxhat is not read.
+template <bool FROZEN>
 __global__ __launch_bounds__(64) void bn_bwd_final_kernel(const double *__restrict__ part, int64_t nch,
                                                           int64_t M, int64_t C, const float *__restrict__ gamma,
                                                           const float *__restrict__ invstd,
@@ -342,10 +349,15 @@ __global__ __launch_bounds__(64) void bn_bwd_final_kernel(const double *__restri
     dgamma[c] = (float)s2;
     sums[c] = s1;
     sums[C + c] = s2;
-    // sum_r dY = gamma*invstd*(s1 - M*(s1/M) - (s2/M)*sum_r xhat): the conv bias gradient
-    if (dbias) dbias[c] = (float)(-(double)gamma[c] * (double)invstd[c] * (s2 / (double)M) * sxhat[c]);
+    if constexpr (FROZEN) {
+        if (dbias) dbias[c] = (float)((double)gamma[c] * (double)invstd[c] * s1);
+    } else {
+        // sum_r dY = gamma*invstd*(s1 - M*(s1/M) - (s2/M)*sum_r xhat): the conv bias gradient
+        if (dbias) dbias[c] = (float)(-(double)gamma[c] * (double)invstd[c] * (s2 / (double)M) * sxhat[c]);
+    }
 }
 
+template <bool FROZEN>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -356,14 +368,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
     if (c >= C) return;
     const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    const float m1 = (float)(sums[c] / (double)M), m2 = (float)(sums[C + c] / (double)M);
+    float m1 = 0.f, m2 = 0.f;
+    if constexpr (!FROZEN) m1 = (float)(sums[c] / (double)M), m2 = (float)(sums[C + c] / (double)M);
     const int64_t r0 = (int64_t)blockIdx.y * kTrEwRows;
     const int64_t r1 = r0 + kTrEwRows < M ? r0 + kTrEwRows : M;
 #pragma unroll 4
     for (int64_t r = r0 + ty; r < r1; r += kTrLanes) {
         float y, xh;
         const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y, xh);
-        dY[r * ldy + c] = ga * is * (d - m1 - xh * m2);
+        if constexpr (FROZEN)
+            dY[r * ldy + c] = ga * is * d;
+        else
+            dY[r * ldy + c] = ga * is * (d - m1 - xh * m2);
     }
 }
 
@@ -438,6 +454,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_vec_kernel(
 }
 
 // dY = gamma * invstd * (dXn - S1/M - xhat * S2/M), dA dense or scattered from the max
+// (FROZEN: dY = gamma * invstd * dXn)
+template <bool FROZEN>
 __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(
     const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -451,7 +469,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         mus[j] = mean[c + j], iss[j] = invstd[c + j], gas[j] = gamma[c + j], bes[j] = beta[c + j];
-        m1[j] = (float)(sums[c + j] / (double)M), m2[j] = (float)(sums[C + c + j] / (double)M);
+        if constexpr (FROZEN)
+            m1[j] = m2[j] = 0.f;
+        else
+            m1[j] = (float)(sums[c + j] / (double)M), m2[j] = (float)(sums[C + c + j] / (double)M);
     }
     const int64_t r0 = (int64_t)blockIdx.y * kTrEwRows;
     constexpr int U = kTrEwRows / kTrVecLanes;  // 4 rows per thread, all in flight
@@ -481,9 +502,145 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(
         for (int j = 0; j < 4; ++j) {
             const float xh = tr_xhat(yv[j], mus[j], iss[j]);
             const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
-            o[j] = gas[j] * iss[j] * (dd - m1[j] - xh * m2[j]);
+            if constexpr (FROZEN)
+                o[j] = gas[j] * iss[j] * dd;
+            else
+                o[j] = gas[j] * iss[j] * (dd - m1[j] - xh * m2[j]);
         }
         *reinterpret_cast<float4 *>(dY + r * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// ---- BatchNorm + ReLU + max over the K rows in one pass over Y (pn2_bn_relu_group_max_f32): the
+// pooled last layer of the frozen-statistics recompute, whose activation A is only needed for
+// its max and argmax.  Each element is bn_relu_apply_kernel's expression (this file is compiled
+// without contraction, so the roundings are the same) and enters the walks of group_max_kernel /
+// group_max_wide_kernel, so out and arg are those of apply followed by pn2_group_max_f32.  No
+// LDS in the narrow kernel, 2 x 4 KiB in the wide one; the kernels read M*C*4 bytes once and
+// write G*C*8: HBM-bound (the A round trip they replace is 2*M*C*4 bytes).
+// W = 1: a thread per column.  W = 4: a thread per 4 adjacent columns, one 16-byte load per row
+// (C, ld, ldo multiples of 4 and 16-byte aligned bases, checked by the host).
+template <int W>
+__device__ __forceinline__ void tr_load_row(const float *p, float (&v)[W]) {
+    if constexpr (W == 4) {
+        const float4 t = ld4(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+__device__ __forceinline__ float tr_act(float y, float mu, float is, float ga, float be, int relu) {
+    const float x = tr_xhat(y, mu, is) * ga + be;
+    return relu ? (x > 0.f ? x : 0.f) : x;
+}
+
+template <int W>
+__device__ __forceinline__ void tr_store_max(float *out, int32_t *arg, const float (&m)[W], const int32_t (&a)[W]) {
+    if constexpr (W == 4) {
+        *reinterpret_cast<float4 *>(out) = make_float4(m[0], m[1], m[2], m[3]);
+        *reinterpret_cast<int4 *>(arg) = make_int4(a[0], a[1], a[2], a[3]);
+    } else {
+        out[0] = m[0];
+        arg[0] = a[0];
+    }
+}
+
+// small K: one thread per (group, W columns); blockIdx.x walks the groups (G has no 65535 limit)
+template <int W>
+__global__ __launch_bounds__(256) void bn_relu_group_max_kernel(
+    const float *__restrict__ Y, int64_t G, int64_t K, int64_t C, int64_t ld, const float *__restrict__ mean,
+    const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ out, int64_t ldo, int32_t *__restrict__ arg, int relu) {
+    constexpr int TX = kTrCols / W, TY = 256 / TX;
+    constexpr int U = W == 4 ? 4 : 8;  // rows in flight
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const int64_t c = (int64_t)blockIdx.y * kTrCols + tx * W;
+    const int64_t g = (int64_t)blockIdx.x * TY + ty;
+    if (c >= C || g >= G) return;  // W == 4: C % 4 == 0, so c < C covers c + 3
+    float mu[W], is[W], ga[W], be[W], m[W];
+    int32_t a[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
+        m[j] = -__builtin_inff(), a[j] = 0x7fffffff;
+    }
+    const float *p = Y + g * K * ld + c;
+    int64_t k = 0;
+    for (; k + U <= K; k += U) {
+        float v[U][W];
+#pragma unroll
+        for (int u = 0; u < U; ++u) tr_load_row<W>(p + (k + u) * ld, v[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                tr_take(tr_act(v[u][j], mu[j], is[j], ga[j], be[j], relu), (int32_t)(k + u), m[j], a[j]);
+    }
+    for (; k < K; ++k) {
+        float v[W];
+        tr_load_row<W>(p + k * ld, v);
+#pragma unroll
+        for (int j = 0; j < W; ++j) tr_take(tr_act(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
+    }
+    tr_store_max<W>(out + g * ldo + c, arg + g * C + c, m, a);
+}
+
+// large K (the group_all layer, K = N): one block per (group, 64 columns), the rows split over
+// kTrWideLanes row lanes merged through LDS, as group_max_wide_kernel
+template <int W>
+__global__ __launch_bounds__(kTrCols / W * kTrWideLanes) void bn_relu_group_max_wide_kernel(
+    const float *__restrict__ Y, int64_t K, int64_t C, int64_t ld, const float *__restrict__ mean,
+    const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ out, int64_t ldo, int32_t *__restrict__ arg, int relu) {
+    __shared__ float sv[kTrWideLanes][kTrCols];
+    __shared__ int32_t sa[kTrWideLanes][kTrCols];
+    constexpr int TX = kTrCols / W;
+    constexpr int U = W == 4 ? 4 : 8;
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const int64_t c = (int64_t)blockIdx.y * kTrCols + tx * W;
+    const int64_t g = blockIdx.x;
+    float m[W];
+    int32_t a[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) m[j] = -__builtin_inff(), a[j] = 0x7fffffff;
+    if (c < C) {
+        float mu[W], is[W], ga[W], be[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
+        const float *p = Y + g * K * ld + c;
+        int64_t k = ty;
+        for (; k + (U - 1) * kTrWideLanes < K; k += U * kTrWideLanes) {
+            float v[U][W];
+#pragma unroll
+            for (int u = 0; u < U; ++u) tr_load_row<W>(p + (k + u * kTrWideLanes) * ld, v[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < W; ++j)
+                    tr_take(tr_act(v[u][j], mu[j], is[j], ga[j], be[j], relu), (int32_t)(k + u * kTrWideLanes),
+                            m[j], a[j]);
+        }
+        for (; k < K; k += kTrWideLanes) {
+            float v[W];
+            tr_load_row<W>(p + k * ld, v);
+#pragma unroll
+            for (int j = 0; j < W; ++j) tr_take(tr_act(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) sv[ty][tx * W + j] = m[j], sa[ty][tx * W + j] = a[j];
+    __syncthreads();
+    // the first 64 threads finish one column each: lane 0 holds row 0 (K >= 1), later lanes may be empty
+    const int col = threadIdx.x;
+    const int64_t cc = (int64_t)blockIdx.y * kTrCols + col;
+    if (col < kTrCols && cc < C) {
+        float bm = sv[0][col];
+        int32_t ba = sa[0][col];
+        for (int l = 1; l < kTrWideLanes; ++l)
+            if (sa[l][col] != 0x7fffffff && tr_better(sv[l][col], sa[l][col], bm, ba)) bm = sv[l][col], ba = sa[l][col];
+        out[g * ldo + cc] = bm;
+        arg[g * C + cc] = ba;
     }
 }
 
@@ -571,20 +728,59 @@ extern "C" int pn2_group_max_f32(const float *A, int64_t G, int64_t K, int64_t C
     return PN2_OK;
 }
 
+template <int W>
+static int launch_bn_relu_group_max(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld, const float *mean,
+                                    const float *invstd, const float *gamma, const float *beta, float *out,
+                                    int64_t ldo, int32_t *arg, int relu, hipStream_t st) {
+    constexpr int TX = kTrCols / W, TY = 256 / TX;
+    const unsigned tiles = (unsigned)((C + kTrCols - 1) / kTrCols);
+    // G < 65536 is not a grid limit here (groups are on grid.x): it keeps the choice of form the
+    // same as pn2_group_max_f32's for every shape, whose wide kernel has its groups on grid.y
+    if (K >= kTrWideK && G < 65536) {
+        hipLaunchKernelGGL(bn_relu_group_max_wide_kernel<W>, dim3((unsigned)G, tiles), dim3(TX * kTrWideLanes), 0, st,
+                           Y, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
+        PN2_LAUNCH_CHECK("bn_relu_group_max_wide_kernel");
+        return PN2_OK;
+    }
+    hipLaunchKernelGGL(bn_relu_group_max_kernel<W>, dim3((unsigned)((G + TY - 1) / TY), tiles), dim3(256), 0, st, Y,
+                       G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
+    PN2_LAUNCH_CHECK("bn_relu_group_max_kernel");
+    return PN2_OK;
+}
+
+extern "C" int pn2_bn_relu_group_max_f32(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld,
+                                         const float *mean, const float *invstd, const float *gamma,
+                                         const float *beta, float *out, int64_t ldo, int32_t *arg, int flags,
+                                         void *stream) {
+    PN2_REQUIRE(Y && mean && invstd && gamma && beta && out && arg, "pn2_bn_relu_group_max_f32: null pointer");
+    PN2_REQUIRE(G >= 0 && K >= 1 && K < ((int64_t)1 << 31) && C >= 1 && ld >= C && ldo >= C,
+                "pn2_bn_relu_group_max_f32: bad shape");
+    PN2_REQUIRE((flags & ~PN2_LAYER_NO_RELU) == 0, "pn2_bn_relu_group_max_f32: unknown flags");
+    if (G == 0) return PN2_OK;
+    const int relu = (flags & PN2_LAYER_NO_RELU) ? 0 : 1;
+    const bool vec4 = (C % 4) == 0 && (ld % 4) == 0 && (ldo % 4) == 0 &&
+                      (((uintptr_t)Y | (uintptr_t)out | (uintptr_t)arg) & 15) == 0;
+    return vec4 ? launch_bn_relu_group_max<4>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
+                                              as_stream(stream))
+                : launch_bn_relu_group_max<1>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
+                                              as_stream(stream));
+}
+
 extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, int64_t ld, const float *mean,
                                         const float *invstd, const float *gamma, const float *beta,
                                         const float *dA, int64_t ldd, const float *dOut, int64_t ldo,
                                         const int32_t *arg, int64_t K, const double *sxhat,
                                         float *dY, int64_t ldy, float *dgamma, float *dbeta,
                                         float *dbias, void *ws, int64_t ws_bytes, int flags, void *stream) {
-    PN2_REQUIRE(Y && mean && invstd && gamma && beta && dY && dgamma && dbeta && ws && (!dbias || sxhat),
+    const bool frozen = (flags & PN2_LAYER_FROZEN_STATS) != 0;  // sxhat is not read
+    PN2_REQUIRE(Y && mean && invstd && gamma && beta && dY && dgamma && dbeta && ws && (!dbias || sxhat || frozen),
                 "pn2_bn_relu_backward_f32: null pointer");
     PN2_REQUIRE(dA || (dOut && arg && K >= 1 && M % K == 0), "pn2_bn_relu_backward_f32: need dA or (dOut, arg, K)");
     PN2_REQUIRE(M >= 1 && M < ((int64_t)1 << 31) && C >= 1 && ld >= C && ldy >= C && (!dA || ldd >= C) &&
                     (dA || ldo >= C),
                 "pn2_bn_relu_backward_f32: bad shape");
     PN2_REQUIRE(ws_bytes >= pn2_bn_train_workspace_bytes(M, C), "pn2_bn_relu_backward_f32: workspace too small");
-    PN2_REQUIRE((flags & ~PN2_LAYER_NO_RELU) == 0, "pn2_bn_relu_backward_f32: unknown flags");
+    PN2_REQUIRE((flags & ~(PN2_LAYER_NO_RELU | PN2_LAYER_FROZEN_STATS)) == 0, "pn2_bn_relu_backward_f32: unknown flags");
     const int relu = (flags & PN2_LAYER_NO_RELU) ? 0 : 1;
     hipStream_t st = as_stream(stream);
     double *part = static_cast<double *>(ws);
@@ -620,17 +816,29 @@ extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, in
                            part);
         PN2_LAUNCH_CHECK("bn_bwd_partial_gather_kernel");
     }
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma,
-                       invstd, sxhat, dbeta, dgamma, dbias, sums);
+    if (frozen)
+        hipLaunchKernelGGL(bn_bwd_final_kernel<true>, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma,
+                           invstd, sxhat, dbeta, dgamma, dbias, sums);
+    else
+        hipLaunchKernelGGL(bn_bwd_final_kernel<false>, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma,
+                           invstd, sxhat, dbeta, dgamma, dbias, sums);
     PN2_LAUNCH_CHECK("bn_bwd_final_kernel");
     const dim3 egrid((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)((M + kTrEwRows - 1) / kTrEwRows));
     if (vec4) {
-        hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma,
-                           beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
+        if (frozen)
+            hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<true>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd,
+                               gamma, beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
+        else
+            hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<false>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd,
+                               gamma, beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
         PN2_LAUNCH_CHECK("bn_bwd_apply_vec_kernel");
     } else {
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma, beta,
-                           dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
+        if (frozen)
+            hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma,
+                               beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
+        else
+            hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma,
+                               beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
         PN2_LAUNCH_CHECK("bn_bwd_apply_kernel");
     }
     return PN2_OK;

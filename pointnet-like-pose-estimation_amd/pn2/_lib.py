@@ -63,6 +63,7 @@ PATH_F32 = 1
 PATH_SPLIT_BF16 = 2
 PATH_BF16 = 3
 LAYER_NO_RELU = 1
+LAYER_FROZEN_STATS = 2
 LINEAR_RELU = 1
 TAIL_LOGSOFTMAX = 1
 DEVERR_NO_NEIGHBOUR = 1
@@ -110,6 +111,8 @@ SIGNATURES = {
     "pn2_bn_relu_backward_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
                                         _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64,
                                         _int, _vp]),
+    "pn2_bn_relu_group_max_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                         _int, _vp]),
     "pn2_prepare_points_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64,
                                       _vp, _vp, _vp]),
     "pn2_prepare_train_points_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64,
@@ -134,7 +137,7 @@ SIGNATURES = {
                                _int, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lib = None
 
 

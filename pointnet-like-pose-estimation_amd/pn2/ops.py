@@ -16,6 +16,8 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
   pn2::group          grouping in sample_and_group :107-116 / the MSG module :204-209
   pn2::pack_layer     Conv2d 1x1 + BatchNorm2d (eval) parameters :150-156, :184-193
   pn2::sa_mlp_max_    gathered shared MLP + max :167-172, :211-218 (writes into `out`)
+  pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
+                      channels-last rows (the recompute of pn2.train's frozen mode)
 """
 import contextlib
 import ctypes
@@ -429,6 +431,16 @@ def _src(mode, points, feature, centers, idx, rows, B, N, C, D, S, K, cnt=None):
     return s
 
 
+MLP_MAX_LAYERS = 4  # csrc/sa_entry.cpp kMaxLayers
+
+
+def sa_mlp_supported(couts) -> bool:
+    """Whether pn2_sa_mlp_max_f32 takes a chain of these layer widths (csrc/sa_entry.cpp
+    validate): at most 4 layers, every width a multiple of 32."""
+    couts = list(couts)
+    return 1 <= len(couts) <= MLP_MAX_LAYERS and all(c >= 32 and c % 32 == 0 for c in couts)
+
+
 def fps_side_job(points: Tensor, npoint: int, start: Tensor):
     """The next SA layer's farthest point sampling as a side job of an SA MLP call (pn2_fps_side):
     points [B,N,C] (any strides), start [B] int64 on the CPU -> (job, (fps_idx, new_points,
@@ -603,3 +615,37 @@ def fc_tail(x: Tensor, layers, logsoftmax: bool):
           p(amax), ws.data_ptr(), nbytes, _stream(x)), x.device,
          flops=2.0 * B * (K * N1 + N1 * N2 + N2 * N3))
     return out, amax
+
+
+# ------------------------------------------------------------------------------ bn_relu_group_max
+def bn_relu_group_max_direct(Y: Tensor, K: int, mean: Tensor, invstd: Tensor, gamma: Tensor, beta: Tensor,
+                             relu: bool) -> Tuple[Tensor, Tensor]:
+    """Y [G*K, C] rows (unit column stride) -> (max [G, C], first argmax [G, C] int32) of
+    act((Y - mean) * invstd * gamma + beta) over each K rows, in one pass over Y
+    (pn2_bn_relu_group_max_f32): the bits of pn2_bn_relu_apply_f32 then pn2_group_max_f32 without
+    the [G*K, C] activation between them.  The pooled last layer of pn2.train's frozen mode."""
+    _dev(Y, "pn2::bn_relu_group_max")
+    M, C = Y.shape
+    if K < 1 or M % K or Y.stride(1) != 1 or any(
+            t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()
+            for t in (mean, invstd, gamma, beta)):
+        raise ValueError("pn2::bn_relu_group_max: Y [G*K, C] with unit column stride and four "
+                         "contiguous float32 [C] vectors")
+    G = M // K
+    out = torch.empty(G, C, dtype=torch.float32, device=Y.device)
+    arg = torch.empty(G, C, dtype=torch.int32, device=Y.device)
+    _run("pn2_bn_relu_group_max_f32", _L.pn2_bn_relu_group_max_f32,
+         (Y.data_ptr(), G, K, C, Y.stride(0), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+          beta.data_ptr(), out.data_ptr(), C, arg.data_ptr(), 0 if relu else _lib.LAYER_NO_RELU,
+          _stream(Y)), Y.device, nbytes=4.0 * M * C + 8.0 * G * C, flops=5.0 * M * C)
+    return out, arg
+
+
+bn_relu_group_max = torch.library.custom_op("pn2::bn_relu_group_max", bn_relu_group_max_direct,
+                                            mutates_args=())
+
+
+@bn_relu_group_max.register_fake
+def _(Y, K, mean, invstd, gamma, beta, relu):
+    G = Y.shape[0] // K
+    return Y.new_empty(G, Y.shape[1]), Y.new_empty(G, Y.shape[1], dtype=torch.int32)

@@ -20,11 +20,16 @@ Training (``model.train()`` or autograd through the weights) keeps the reference
 query still run as HIP kernels (they are index ops with no gradient); in train mode the
 grouping and the MLP + max run forward and backward on the training kernels of pn2/train.py
 (csrc/train.hip around library GEMMs).  As in the reference, an eval-mode forward with
-autograd enabled (``model.eval()`` without ``torch.no_grad()``, parameters requiring grad) is
-differentiable: it runs the torch device formulation.  The fused inference kernels serve
-eval-mode forwards under ``torch.no_grad()`` / ``torch.inference_mode()``, with parameters that
-need no gradient, or inside ``pn2.fused_eval()`` (the mutilthreading/predict_test.py pattern
-made fast: its outputs carry no autograd history).
+autograd enabled (``model.eval()`` without ``torch.no_grad()``, parameters requiring grad: the
+mutilthreading/predict_test.py pattern, or fine-tuning with frozen BatchNorm) is
+differentiable.  Its forward is the fused forward above -- the launches, the CPU-RNG draws and
+the bits of the no_grad forward -- inside an autograd Function (_SaEvalGrad) that saves the
+inputs, the centroids and the neighbour lists, no activation; its backward recomputes the layer
+on the frozen-statistics training kernels (train.mlp_max_frozen) and gives the gradients of
+the reference's eval formulation to the conv / BN parameters and the input feature.  The torch
+device formulation remains for what that route does not cover (_eval_grad_route) and under
+tuning ``eval_grad=0``.  Inside ``pn2.fused_eval()`` the fused forward runs without autograd
+history.
 
 Device tensors only -- the reference's CPU execution is not re-implemented here.
 """
@@ -52,14 +57,19 @@ def _draw_start(B, N, device):
     return shard.host_start(B, N, device)
 
 
-def _fps_ahead(module, new_points):
+def _fps_ahead(module, new_points, live=False):
     """The side job that runs the next SA layer's FPS (geometry.fps_ahead) on this layer's
     centroids `new_points` [B, S, C] inside this layer's MLP call, or None: registered so the next
-    layer's forward takes its results instead of sampling."""
+    layer's forward takes its results instead of sampling.  live: this layer runs inside
+    _SaEvalGrad (autograd is on around it and its output will require grad, so the next layer's
+    forward is a differentiable one); the next layer then takes the results only on that route
+    too -- the torch formulation samples for itself."""
     nxt = geometry.ahead_of(module)
     if nxt is None or getattr(nxt, "group_all", False) or nxt.point_number is None:
         return None
-    if _needs_autograd(nxt, new_points) or shard.recording():  # (graph records: device starts)
+    if (live or _needs_autograd(nxt, new_points)) and not _eval_grad_route(nxt, new_points, None):
+        return None
+    if shard.recording():  # (graph records: device starts)
         return None
     B, N, _ = new_points.shape
     start = shard.host_start(B, N, new_points.device)
@@ -99,7 +109,7 @@ def fused_eval(enabled=True):
     with autograd enabled (``model.eval()`` without ``torch.no_grad()``, the
     mutilthreading/predict_test.py pattern): the no_grad bits, no autograd history (a backward
     through the outputs finds nothing that requires grad).  Outside it such a forward is
-    differentiable, as in the reference."""
+    differentiable, as in the reference (the SA layers with the same bits, _SaEvalGrad)."""
     prev = getattr(_fused, "on", False)
     _fused.on = bool(enabled)
     try:
@@ -127,6 +137,98 @@ def _needs_autograd(module, *tensors):
     if any(t is not None and t.requires_grad for t in tensors):
         return True
     return any(p.requires_grad for p in module.parameters())
+
+
+def _eval_grad_route(module, points, feature):
+    """Whether an eval-mode SA forward that must be differentiable runs the fused inference
+    kernels with the recompute backward (_SaEvalGrad).  Everything else stays the reference's
+    torch formulation (_forward_autograd)."""
+    if module.training or not tuning.get("eval_grad"):  # eval_grad=0: the torch formulation
+        return False
+    if points.requires_grad:  # coordinates that need a gradient: torch gathers carry it
+        return False
+    if not points.is_cuda or any(t is not None and t.dtype != torch.float32 for t in (points, feature)):
+        return False  # non-float32 tensors (or host tensors): torch formulation
+    if _precision(module) != "fp32":  # bf16 forward: the float32 recompute is another function
+        return False
+    if isinstance(module, PointNetSetAbstractionMsg):
+        blocks = list(zip(module.conv_blocks, module.bn_blocks))
+    else:
+        blocks = [(module.mlp_convs, module.mlp_bns)]
+    for convs, _ in blocks:  # shapes the fused MLP entry rejects (widths not x32, > 4 layers)
+        if not ops.sa_mlp_supported(c.weight.shape[0] for c in convs):
+            return False
+    # non-float32 parameters, BN without running statistics or affine, convs without bias or
+    # not 1x1 (train.eligible_frozen names each): torch formulation
+    return all(train.eligible_frozen(points, convs, bns) for convs, bns in blocks)
+
+
+def _frozen_group(points, idx, centers, feature, feature_first):
+    """The grouped rows of the recompute from the forward's int32 neighbour lists: with the
+    index_add_ backward when the features need a gradient, else the plain grouping kernel."""
+    idx = idx.long()
+    g = train.group_train(points, idx, centers, feature, feature_first)
+    return g if g is not None else ops.group_direct(points, feature, centers, idx, feature_first)
+
+
+def _versions(module):
+    """What _SaEvalGrad's recompute reads besides the saved tensors: the in-place versions of the
+    parameters and the BatchNorm buffers, and the eval flags."""
+    return (tuple(p._version for p in module.parameters()) + tuple(b._version for b in module.buffers()) +
+            tuple(m.training for m in module.modules()))
+
+
+class _SaEvalGrad(torch.autograd.Function):
+    """An SA module's eval-mode forward under autograd: the forward is the module's fused body
+    (the launches, the CPU-RNG draws and the bits of the no_grad forward); nothing of the MLP is
+    saved -- only the inputs, the centroids and the neighbour lists the forward made.  The
+    backward recomputes the layer from those on the frozen-statistics training kernels
+    (train.mlp_max_frozen: library GEMMs + csrc/train.hip) and backpropagates through that:
+    gradients of the reference's eval formulation (pointnet2_utils.py:163-172 / :211-221 with
+    BatchNorm2d on its running statistics) for the conv / BN parameters and the input feature.
+    FPS and ball query are not re-run and no RNG draw is taken."""
+
+    @staticmethod
+    def forward(ctx, module, points, feature, *params):
+        new_points, out, centers, idxs = module._fused_body(points, feature, live=True)
+        ctx.module = module  # parameter references: the recompute reads the live parameters
+        ctx.versions = _versions(module)
+        ctx.save_for_backward(points, feature, centers, *idxs)
+        ctx.mark_non_differentiable(new_points)
+        return new_points, out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _dnew_points, dout):
+        module = ctx.module
+        params = list(module.parameters())
+        if _versions(module) != ctx.versions:
+            raise RuntimeError("pn2: a parameter or buffer of %s was modified in place, or the module "
+                               "left eval mode, between the eval-mode forward and its backward (the "
+                               "backward recomputes the layer from them)" % type(module).__name__)
+        points, feature, centers, *idxs = ctx.saved_tensors
+        with torch.enable_grad():
+            leaf = None
+            if feature is not None:
+                leaf = feature.detach().requires_grad_(ctx.needs_input_grad[2])
+            out = module._recompute(points.detach(), leaf, centers, idxs)  # [B, Cout, S]
+            B, cout, S = out.shape
+            wanted = [i for i, p in enumerate(params) if ctx.needs_input_grad[3 + i]]
+            inputs = [params[i] for i in wanted]
+            if leaf is not None and leaf.requires_grad:
+                inputs.append(leaf)
+            got = torch.autograd.grad([out], inputs, [dout.reshape(B, S, cout).permute(0, 2, 1)],
+                                      allow_unused=True)
+        grads = [None] * len(params)
+        for i, g in zip(wanted, got):
+            grads[i] = g
+        dfeat = got[-1] if len(inputs) > len(wanted) else None
+        return (None, None, dfeat, *grads)
+
+
+def _eval_grad_forward(module, points, feature):
+    new_points, out = _SaEvalGrad.apply(module, points, feature, *module.parameters())
+    return module._views(new_points, out)
 
 
 _SPLIT_MAX_XYZ = 16  # point channels of a split-bf16 first layer (csrc/sa_chain.hip)
@@ -183,8 +285,8 @@ def _torch_group(points, idx, centers, feature, feature_first):
 
 def _torch_mlp_max(grouped, convs, bns):
     """grouped [B,S,K,C] -> [B, Cout, S].  Training on the device: the fused batch-statistics
-    BN / ReLU / max kernels around library GEMMs (pn2/train.py); otherwise (eval with autograd,
-    exotic BN configs) the reference's torch formulation."""
+    BN / ReLU / max kernels around library GEMMs (pn2/train.py); otherwise (eval with autograd
+    where _eval_grad_route does not apply, exotic BN configs) the reference's torch formulation."""
     if train.eligible(grouped, convs, bns):
         return train.mlp_max_train(grouped, convs, bns)
     x = grouped.permute(0, 3, 2, 1)  # [B, C, K, S] as the reference (:167)
@@ -267,7 +369,22 @@ class PointNetSetAbstraction(nn.Module):
         """points [B,C,N], feature [B,D,N] or None -> (new_points [B,C,S], new_feature
         [B,mlp[-1],S]).  Both outputs are channel-first views of channels-last buffers."""
         if _needs_autograd(self, points, feature):
+            if _eval_grad_route(self, points, feature):
+                return _eval_grad_forward(self, points, feature)
             return self._forward_autograd(points, feature)
+        new_points, out, _, _ = self._fused_body(points, feature)
+        return self._views(new_points, out)
+
+    def _views(self, new_points, out):
+        """The fused body's buffers as the forward's channel-first outputs."""
+        B, cout = new_points.shape[0], out.shape[-1]
+        if self.group_all:
+            return new_points, out.view(B, 1, cout).permute(0, 2, 1)
+        return new_points.permute(0, 2, 1), out.view(B, -1, cout).permute(0, 2, 1)
+
+    def _fused_body(self, points, feature, live=False):
+        """The fused inference launches (the no_grad forward and _SaEvalGrad's forward) ->
+        (new_points buffer, out rows, centroids [B,S,C] or None, [int32 neighbour lists])."""
         pts = points.permute(0, 2, 1)
         feat = None if feature is None else _channels_last(feature)
         B, N, C = pts.shape
@@ -284,7 +401,7 @@ class PointNetSetAbstraction(nn.Module):
             new_points = torch.empty(B, C, 1, device=dev, dtype=torch.float32)
             ops.sa_mlp_max_direct(out, _lib.SRC_GROUP_ALL, pts, feat, None, None, wts, als, bes, cins,
                                   splits, _precision(self), zero=new_points)
-            return new_points, out.view(B, 1, cout).permute(0, 2, 1)
+            return new_points, out, None, []
         S, K = self.point_number, self.sample_number
         pre = geometry.take(self, pts)  # FPS (+ ball query) precomputed by pn2.pipeline
         if pre is not None:
@@ -297,8 +414,20 @@ class PointNetSetAbstraction(nn.Module):
             span.finish([new_points], [new_points, idx, cnt])
         out = torch.empty(B * S, cout, device=dev, dtype=torch.float32)
         ops.sa_mlp_max_impl(out, _lib.SRC_GROUP_XYZ_FIRST, pts, feat, new_points, idx, wts, als, bes,
-                            cins, splits, _precision(self), cnt=cnt, fps_side=_fps_ahead(self, new_points))
-        return new_points.permute(0, 2, 1), out.view(B, S, cout).permute(0, 2, 1)
+                            cins, splits, _precision(self), cnt=cnt,
+                            fps_side=_fps_ahead(self, new_points, live))
+        return new_points, out, new_points, [idx]
+
+    def _recompute(self, points, feature, centers, idxs):
+        """The layer again from the forward's centroids and lists, differentiable in `feature`
+        and the parameters, on the frozen-statistics training kernels -> [B, Cout, S]."""
+        pts = points.permute(0, 2, 1)
+        feat = None if feature is None else feature.permute(0, 2, 1)
+        if self.group_all:  # plain rows in the reference's [xyz | feature] order (:139)
+            grouped = sample_and_group_all(pts, feat)[1]
+        else:
+            grouped = _frozen_group(pts, idxs[0], centers, feat, False)
+        return train.mlp_max_frozen(grouped, self.mlp_convs, self.mlp_bns)
 
     def _forward_autograd(self, points, feature):
         pts = points.permute(0, 2, 1)
@@ -340,7 +469,19 @@ class PointNetSetAbstractionMsg(nn.Module):
 
     def forward(self, points, feature):
         if _needs_autograd(self, points, feature):
+            if _eval_grad_route(self, points, feature):
+                return _eval_grad_forward(self, points, feature)
             return self._forward_autograd(points, feature)
+        new_points, out, _, _ = self._fused_body(points, feature)
+        return self._views(new_points, out)
+
+    def _views(self, new_points, out):
+        B, total = new_points.shape[0], out.shape[-1]
+        return new_points.permute(0, 2, 1), out.view(B, -1, total).permute(0, 2, 1)
+
+    def _fused_body(self, points, feature, live=False):
+        """The fused inference launches of all scales (the no_grad forward and _SaEvalGrad's
+        forward) -> (new_points [B,S,C], out rows, centroids, [int32 lists per scale])."""
         pts = points.permute(0, 2, 1)
         feat = None if feature is None else _channels_last(feature)
         B, N, C = pts.shape
@@ -364,7 +505,7 @@ class PointNetSetAbstractionMsg(nn.Module):
         out = torch.empty(B * S, total, device=dev, dtype=torch.float32)
         prec = _precision(self)
         col = 0
-        side = _fps_ahead(self, new_points)  # rides on the longest scale's launch (largest K)
+        side = _fps_ahead(self, new_points, live)  # rides on the longest scale's launch (largest K)
         longest = max(range(len(idxs)), key=lambda i: self.sample_number_list[i])
         for i, (idx, cnt) in enumerate(idxs):
             wts, als, bes, cins, splits = chains[i]
@@ -373,7 +514,18 @@ class PointNetSetAbstractionMsg(nn.Module):
                                 new_points, idx, wts, als, bes, cins, splits, prec, cnt=cnt,
                                 fps_side=side if i == longest else None)
             col += cout
-        return new_points.permute(0, 2, 1), out.view(B, S, total).permute(0, 2, 1)
+        return new_points, out, new_points, [idx for idx, _ in idxs]
+
+    def _recompute(self, points, feature, centers, idxs):
+        """Every scale again from the forward's centroids and lists (one Function for the module:
+        autograd sums the scales' feature gradients) -> [B, sum Cout, S]."""
+        pts = points.permute(0, 2, 1)
+        feat = None if feature is None else feature.permute(0, 2, 1)
+        outs = []
+        for i, idx in enumerate(idxs):
+            grouped = _frozen_group(pts, idx, centers, feat, True)
+            outs.append(train.mlp_max_frozen(grouped, self.conv_blocks[i], self.bn_blocks[i]))
+        return torch.cat(outs, dim=1)
 
     def _forward_autograd(self, points, feature):
         pts = points.permute(0, 2, 1)

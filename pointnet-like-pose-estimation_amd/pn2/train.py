@@ -19,8 +19,15 @@ same computation on [M = B*N, C] rows with K = N (the max over a cloud's points)
 (PN2_LAYER_NO_RELU): point_mlp_train.
 
 Used by the SA modules' and the v1 modules' autograd path when a module is training on a ROCm
-device (pn2/pointnet2_utils.py, pn2/pointnet_utils.py, pn2/heads_v1.py); eval with autograd
-keeps the reference's torch formulation.
+device (pn2/pointnet2_utils.py, pn2/pointnet_utils.py, pn2/heads_v1.py).
+
+Frozen mode (mlp_max_frozen): the same rows with eval-mode BatchNorm -- mean = running_mean,
+invstd = rsqrt(running_var + eps), constants of the backward (PN2_LAYER_FROZEN_STATS), no
+running-stat update, no counter increment.  Hidden layers run pn2_bn_relu_apply_f32; the pooled
+last layer runs pn2_bn_relu_group_max_f32, which keeps Y and never writes its activation.  The
+SA modules' eval-mode forward under autograd recomputes a layer with it in its backward
+(pn2/pointnet2_utils.py); the v1 modules' eval forward with autograd keeps the reference's
+torch formulation.
 """
 import torch
 
@@ -39,6 +46,23 @@ def eligible(grouped, convs, bns):
             return False
         if not bn.training:
             return False
+    return True
+
+
+def eligible_frozen(grouped, convs, bns):
+    """The frozen-statistics path covers: float32 device rows and parameters, 1x1 convs with
+    bias, affine eval-mode BN that has running statistics."""
+    if not grouped.is_cuda or grouped.dtype != torch.float32:  # non-float32 (or host) rows
+        return False
+    for conv, bn in zip(convs, bns):
+        if conv.bias is None or tuple(conv.weight.shape[2:]) not in ((1, 1), (1,)):
+            return False  # convs without bias, or not 1x1
+        if not bn.affine:  # non-affine BN: no gamma / beta to pass or to differentiate
+            return False
+        if bn.training or bn.running_mean is None or bn.running_var is None:
+            return False  # BN without running statistics (or in train mode: mlp_max_train's)
+        if any(t.dtype != torch.float32 for t in (conv.weight, bn.weight, bn.running_mean)):
+            return False  # non-float32 parameters
     return True
 
 
@@ -93,18 +117,35 @@ class _MlpMaxTrain(torch.autograd.Function):
     def forward(ctx, x0, K, cfg, *params):
         """x0 [M, Cin] rows; cfg[l] = (eps, momentum factor, running_mean, running_var, flags);
         params = (W, b, gamma, beta) per layer.  -> [M / K, Cout] max over each K rows, or the
-        last layer's [M, Cout] rows when K == 0."""
+        last layer's [M, Cout] rows when K == 0.  A layer whose flags carry LAYER_FROZEN_STATS
+        normalises with (running_mean, rsqrt(running_var + eps)) and updates nothing."""
         L = _lib.load()
         n = len(cfg)
         M = x0.shape[0]
         st = _stream(x0)
         xs, ys, stats = [x0], [], []
-        x = x0
+        x, pooled = x0, None
         for l in range(n):
             W, b, g, be = params[4 * l:4 * l + 4]
             eps, mom, rm, rv, flags = cfg[l]
             cout = W.shape[0]
             Y = torch.addmm(b, x, W.reshape(cout, -1).t())
+            if flags & _lib.LAYER_FROZEN_STATS:
+                mean, invstd = rm, torch.rsqrt(rv + eps)
+                ys.append(Y)
+                stats += [mean, invstd, None]  # no sxhat: the backward's sums need none
+                if l == n - 1 and K:  # max and argmax straight from Y: A is never written
+                    pooled, arg = ops.bn_relu_group_max_direct(Y, K, mean, invstd, g, be,
+                                                               not flags & _lib.LAYER_NO_RELU)
+                    continue
+                ptrs = (mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), be.data_ptr())
+                x = torch.empty_like(Y)
+                _lib.check(L.pn2_bn_relu_apply_f32(
+                    Y.data_ptr(), M, cout, cout, *ptrs, x.data_ptr(), cout,
+                    flags & _lib.LAYER_NO_RELU, st), "pn2_bn_relu_apply_f32")
+                if l + 1 < n:
+                    xs.append(x)
+                continue
             ws = _workspace(L, M, cout, x0.device, st)
             st_mi = torch.empty(2 * cout, device=x0.device)  # [mean | invstd]
             sxhat = torch.empty(cout, dtype=torch.float64, device=x0.device)
@@ -125,6 +166,9 @@ class _MlpMaxTrain(torch.autograd.Function):
         if not K:
             ctx.save_for_backward(*xs, *ys, *stats, *params)
             return x
+        if pooled is not None:
+            ctx.save_for_backward(*xs, *ys, *stats, arg, *params)
+            return pooled
         G = M // K
         cout = x.shape[1]
         out = torch.empty(G, cout, device=x0.device)
@@ -164,7 +208,7 @@ class _MlpMaxTrain(torch.autograd.Function):
                 Y.data_ptr(), M, cout, cout, mean.data_ptr(), invstd.data_ptr(), g.data_ptr(),
                 be.data_ptr(), 0 if last else dA.data_ptr(), cout,
                 dout.data_ptr() if last else 0, cout, arg.data_ptr() if last else 0, K,
-                sxhat.data_ptr(), dY.data_ptr(), cout, dgamma.data_ptr(), dbeta.data_ptr(),
+                0 if sxhat is None else sxhat.data_ptr(), dY.data_ptr(), cout, dgamma.data_ptr(), dbeta.data_ptr(),
                 dbias.data_ptr(), ws.data_ptr(), ws.numel(), ctx.flags[l], st),
                 "pn2_bn_relu_backward_f32")
             X = xs[l]
@@ -224,6 +268,23 @@ def _apply(x0, K, convs, bns, last_relu=True):
     return _MlpMaxTrain.apply(x0, K, tuple(cfg), *params)
 
 
+def mlp_max_frozen(grouped, convs, bns):
+    """mlp_max_train's contract with eval-mode (running-statistics) BatchNorm: grouped
+    [B, S, K, Cin] -> [B, Cout, S], the reference's ``torch.max(relu(bn(conv(x)))..., 2)[0]`` of
+    an eval-mode layer (:167-172), differentiable in the features and the conv / BN parameters.
+    Running statistics and num_batches_tracked are read only."""
+    B, S, K, Cin = grouped.shape
+    x0 = grouped.reshape(B * S * K, Cin)
+    if not x0.is_contiguous():
+        x0 = x0.contiguous()
+    cfg, params = [], []
+    for conv, bn in zip(convs, bns):
+        cfg.append((float(bn.eps), 0.0, bn.running_mean, bn.running_var, _lib.LAYER_FROZEN_STATS))
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    out = _MlpMaxTrain.apply(x0, K, tuple(cfg), *params)
+    return out.view(B, S, -1).permute(0, 2, 1)
+
+
 def mlp_max_train(grouped, convs, bns):
     """grouped [B, S, K, Cin] (any float32 device tensor, autograd-tracked) -> [B, Cout, S]:
     the reference's ``torch.max(relu(bn(conv(x)))..., 2)[0]`` in train mode (:167-172)."""
@@ -253,4 +314,5 @@ def point_mlp_train(x, convs, bns, rows, pool=True, last_relu=True):
     return out if pool else out.view(B, N, -1)
 
 
-__all__ = ["mlp_max_train", "point_mlp_train", "group_train", "eligible"]
+__all__ = ["mlp_max_train", "mlp_max_frozen", "point_mlp_train", "group_train", "eligible",
+           "eligible_frozen"]

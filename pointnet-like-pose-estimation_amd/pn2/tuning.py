@@ -25,6 +25,9 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      its batches side by side; 0: one forward per batch
     bq_multi         1: an MSG layer's ball queries in one launch over its radii
                      (pn2_ball_query_multi_i32); 0: one launch per radius
+    eval_grad        1: an SA module's eval-mode forward under autograd runs the fused inference
+                     kernels and recomputes the layer in its backward (pointnet2_utils
+                     _SaEvalGrad); 0: the reference's torch formulation
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -51,6 +54,7 @@ HOST_DEFAULTS = {
     "geometry_bq": 1,
     "pipe_fuse": 1,
     "bq_multi": 1,
+    "eval_grad": 1,
 }
 
 
