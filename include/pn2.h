@@ -55,6 +55,11 @@
  *                          (random_point_dropout, random_scale_point_cloud, shift_point_cloud)
  *                                                            provider.py:131-164;
  *                                                            train_translation.py:109-119
+ *   pn2_fps_points         the numpy farthest_point_sample(point_cloud, number) of the data path
+ *                                                            provider.py:183-204;
+ *                                                            data_utils/ModelNetDataLoader.py:25-46;
+ *                                                            point_collect/transformer.py:120-141;
+ *                                                            data_build/Cube.py:102-123
  */
 #ifndef PN2_H
 #define PN2_H
@@ -152,6 +157,36 @@ int pn2_fps_host_ws_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64
                         int64_t sc, const int64_t *start_host, int64_t S, int64_t *out_idx,
                         float *out_pts, float *out_packed, float *pts_packed, void *workspace,
                         int64_t workspace_bytes, void *stream);
+
+/* ---- farthest-point downsampling of raw clouds by the reference's NUMPY rule
+ * (provider.py:183-204 and its copies; csrc/fps_points.hip), a ragged batch in one launch.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ *   pts       [total_rows][ld] rows of `dtype` elements (PN2_DTYPE_F32 / PN2_DTYPE_F64), ld >= C;
+ *             cloud b is the rows offsets[b] .. offsets[b+1]-1
+ *   offsets   [B+1] int64 row offsets (device), 0 <= offsets[b] < offsets[b+1] <= total_rows,
+ *             every cloud of 1 .. max_n rows;  starts [B] int64 (device), the reference's
+ *             np.random.randint(0, N) draw of each cloud
+ *   out_idx   [B][S] int64: the sampled row of each of the S iterations (S may exceed a cloud's N:
+ *             the reference then repeats indices);  out_pts [B][S][C] `dtype`: point_cloud[idx],
+ *             all C columns.  Only columns 0..2 are measured.
+ * Arithmetic in the input's precision, every operation rounded separately: d_k = x_k - c_k,
+ * dist = (d_0*d_0 + d_1*d_1) + d_2*d_2, running distance 1e10 at the start and replaced only when
+ * dist < distance, next centroid the FIRST index of the maximum.  Inputs must be finite.
+ * One 1024-thread workgroup per cloud.  Two paths, chosen per launch by max_n: the running
+ * distances live in LDS while max_n <= (160 KiB - 384) / sizeof(element) (40864 float32, 20432
+ * float64 points), else in `workspace`, one element per input row.
+ * pn2_fps_points_workspace_bytes(dtype, total_rows, max_n) reports the path: 0 on the LDS path,
+ * total_rows * sizeof(element) past it (-1: bad arguments).  The workspace is 8-byte aligned.
+ * A cloud whose table entries break the rules above (or whose start is outside [0, N)) is not
+ * sampled: its out_idx row is -1, its out_pts rows are not written, PN2_DEVERR_INDEX is raised.
+ * B == 0 or S == 0: nothing to do, no launch. */
+#define PN2_DTYPE_F32 0
+#define PN2_DTYPE_F64 1
+int64_t pn2_fps_points_workspace_bytes(int dtype, int64_t total_rows, int64_t max_n);
+int pn2_fps_points(const void *pts, int dtype, int64_t B, const int64_t *offsets,
+                   const int64_t *starts, int64_t total_rows, int64_t max_n, int64_t C, int64_t ld,
+                   int64_t S, int64_t *out_idx, void *out_pts, void *workspace,
+                   int64_t workspace_bytes, void *stream);
 
 /* Pack a [B,N,C] strided view into [B,N,cp] with its ssq (see above).  C <= 64, as for the
  * ball query and square_distance below (else PN2_EUNSUPPORTED). */

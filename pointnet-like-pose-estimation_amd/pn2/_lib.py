@@ -68,6 +68,8 @@ LINEAR_RELU = 1
 TAIL_LOGSOFTMAX = 1
 DEVERR_NO_NEIGHBOUR = 1
 DEVERR_INDEX = 2
+DTYPE_F32 = 0
+DTYPE_F64 = 1
 
 # name -> (restype, argtypes); every symbol include/pn2.h declares
 SIGNATURES = {
@@ -80,6 +82,9 @@ SIGNATURES = {
                               _i64, _vp]),
     "pn2_fps_host_ws_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                                    _vp, _i64, _vp]),
+    "pn2_fps_points_workspace_bytes": (_i64, [_int, _i64, _i64]),
+    "pn2_fps_points": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64,
+                              _vp]),
     "pn2_pack_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pn2_ball_query_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
     "pn2_ball_query_cnt_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp]),

@@ -204,4 +204,152 @@ def prepare_train_batch(points, label=None, num_category=7, with_mean=False, nor
     return out.transpose(2, 1), mean
 
 
-__all__ = ["prepare_batch", "prepare_train_batch", "draw_augmentation", "Augmentation"]
+# ------------------------------------------------------------- farthest-point downsampling
+# The reference's numpy farthest_point_sample(point_cloud, number) (provider.py:183-204, the same
+# function in data_utils/ModelNetDataLoader.py:25-46, point_collect/transformer.py:120-141 and
+# data_build/*.py), which every cloud passes through before it reaches a model: one launch of
+# csrc/fps_points.hip for a whole ragged batch, in the clouds' own dtype, bit for bit.
+_DOWNSAMPLE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float64: _lib.DTYPE_F64}
+
+
+def _host_clouds(who, clouds):
+    """A list of [N_i, C] arrays (or one [B, N, C] array) -> (rows [sum N_i, C], sizes)."""
+    if isinstance(clouds, np.ndarray):
+        if clouds.ndim != 3:
+            raise ValueError("pn2.provider.%s: an array of clouds must be [B, N, C]" % who)
+        clouds = list(clouds)
+    clouds = [np.asarray(c) for c in clouds]
+    if not clouds:
+        raise ValueError("pn2.provider.%s: no clouds" % who)
+    first = clouds[0]
+    for c in clouds:
+        if c.ndim != 2:
+            raise ValueError("pn2.provider.%s: every cloud must be [N, C]" % who)
+        if c.dtype != first.dtype or c.shape[1] != first.shape[1]:
+            raise ValueError("pn2.provider.%s: the clouds of one batch share dtype and C" % who)
+    if first.dtype not in (np.float32, np.float64):
+        raise TypeError("pn2.provider.%s: clouds must be float64 or float32, got %s" % (who, first.dtype))
+    if first.shape[1] < 3:
+        raise ValueError("pn2.provider.%s: needs C >= 3 (xyz), got C = %d" % (who, first.shape[1]))
+    return clouds
+
+
+def _draw_starts(who, sizes, starts):
+    """starts=None: one np.random.randint(0, N) per cloud in list order (an empty cloud raises
+    numpy's ValueError there, as in the reference).  Given starts are range-checked here."""
+    if starts is None:
+        return np.array([np.random.randint(0, n) for n in sizes], dtype=np.int64)
+    st = np.asarray(starts).reshape(-1)
+    if st.size != len(sizes):
+        raise ValueError("pn2.provider.%s: %d starts for %d clouds" % (who, st.size, len(sizes)))
+    st = st.astype(np.int64)
+    for b, (s, n) in enumerate(zip(st.tolist(), sizes)):
+        if s < 0 or s >= n:
+            raise IndexError("pn2.provider.%s: start %d of cloud %d is out of bounds for %d points"
+                             % (who, s, b, n))
+    return st
+
+
+def _fps_points_launch(rows, ld, C, offsets, starts, total_rows, max_n, number):
+    """rows: a device tensor whose data_ptr is row 0.  -> (idx [B, number], pts [B, number, C])."""
+    dev = rows.device
+    B = len(starts)
+    with torch.cuda.device(dev):
+        table = torch.from_numpy(np.concatenate([offsets, starts])).pin_memory().to(dev, non_blocking=True)
+        idx = torch.empty(B, number, dtype=torch.int64, device=dev)
+        out = torch.empty(B, number, C, dtype=rows.dtype, device=dev)
+        if B and number:
+            L = _lib.load()
+            code = _DOWNSAMPLE_DTYPES[rows.dtype]
+            need = L.pn2_fps_points_workspace_bytes(code, total_rows, max_n)
+            if need < 0:
+                raise ValueError("pn2.provider.farthest_point_sample_batch: bad batch shape")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+            _lib.check(L.pn2_fps_points(
+                rows.data_ptr(), code, B, table.data_ptr(), table.data_ptr() + 8 * (B + 1), total_rows,
+                max_n, C, ld, number, idx.data_ptr(), out.data_ptr(), 0 if ws is None else ws.data_ptr(),
+                need, _stream(out)), "pn2_fps_points")
+    return idx, out
+
+
+def farthest_point_sample_batch(clouds, number=1024, starts=None, return_index=False, device=None):
+    """The reference's farthest_point_sample for a whole batch in one launch.
+
+    clouds: a list of [N_i, C] numpy arrays (ragged), one [B, N, C] numpy array, or a [B, N, C]
+    torch tensor on a ROCm device; float64 or float32, C >= 3.  Only columns 0..2 are measured;
+    every column is carried into the result.
+    starts: None draws one np.random.randint(0, N_i) per cloud, in order -- what calling the
+    reference in a loop consumes; else [B] start rows, checked on the host (IndexError before
+    any launch).
+    Returns point_cloud[idx] per cloud as [B, number, C] in the input's dtype (with
+    return_index, also the int64 [B, number] rows picked): numpy arrays for host input, device
+    tensors for a device tensor -- no host round trip, ready for prepare_batch.
+    Host coordinates must be finite (ValueError): the kernel orders distances by their bit
+    patterns, which differs from numpy on NaN.  A device tensor is not checked (that would
+    synchronise)."""
+    who = "farthest_point_sample_batch"
+    number = int(number)
+    if number < 0:
+        raise ValueError("negative dimensions are not allowed")
+    if isinstance(clouds, torch.Tensor):
+        t = clouds
+        if t.dim() != 3:
+            raise ValueError("pn2.provider.%s: a tensor of clouds must be [B, N, C]" % who)
+        if t.dtype not in _DOWNSAMPLE_DTYPES:
+            raise TypeError("pn2.provider.%s: clouds must be float64 or float32, got %s" % (who, t.dtype))
+        B, N, C = t.shape
+        if C < 3:
+            raise ValueError("pn2.provider.%s: needs C >= 3 (xyz), got C = %d" % (who, C))
+        st = _draw_starts(who, [N] * B, starts)
+        dev = _pick_device(who, t, device)
+        t = t.to(dev, non_blocking=True)
+        # rows of one stride, clouds a whole number of rows apart; else one packed copy
+        if B and N and not (t.stride(2) == 1 and t.stride(1) >= C and t.stride(0) % t.stride(1) == 0
+                            and t.stride(0) >= N * t.stride(1)):
+            t = t.contiguous()
+        if B == 0 or N == 0:
+            idx = torch.empty(B, number, dtype=torch.int64, device=dev)
+            out = torch.empty(B, number, C, dtype=t.dtype, device=dev)
+        else:
+            ld, step = t.stride(1), t.stride(0) // t.stride(1)
+            offsets = np.arange(B + 1, dtype=np.int64) * step
+            offsets[B] = (B - 1) * step + N
+            idx, out = _fps_points_launch(t, ld, C, offsets, st, int(offsets[B]), N, number)
+        return (out, idx) if return_index else out
+    clouds = _host_clouds(who, clouds)
+    sizes = [len(c) for c in clouds]
+    st = _draw_starts(who, sizes, starts)
+    C = clouds[0].shape[1]
+    for b, c in enumerate(clouds):
+        if not np.isfinite(c[:, :3]).all():
+            raise ValueError("pn2.provider.%s: cloud %d has a NaN or infinite coordinate" % (who, b))
+    dev = _pick_device(who, torch.empty(0), device)
+    offsets = np.zeros(len(clouds) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    total = int(offsets[-1])
+    stage = torch.empty(total, C, dtype=torch.from_numpy(clouds[0][:0]).dtype, pin_memory=True)
+    np.concatenate(clouds, 0, out=stage.numpy())
+    with torch.cuda.device(dev):
+        rows = stage.to(dev, non_blocking=True)
+    idx, out = _fps_points_launch(rows, C, C, offsets, st, total, max(sizes), number)
+    out = out.cpu().numpy()
+    return (out, idx.cpu().numpy()) if return_index else out
+
+
+def farthest_point_sample(point_cloud, number=1024):
+    """The reference's farthest_point_sample(point_cloud, number) (provider.py:183-204;
+    ModelNetDataLoader's (point, npoint) works positionally): point_cloud [N, C] numpy, float64
+    or float32 -> point_cloud[idx], [number, C] in the same dtype, for the same state of numpy's
+    global generator, of which it consumes exactly one np.random.randint(0, N)."""
+    point_cloud = np.asarray(point_cloud)
+    if point_cloud.ndim != 2:
+        raise ValueError("pn2.provider.farthest_point_sample: point_cloud must be [N, C], got shape %s"
+                         % (tuple(point_cloud.shape),))
+    C = point_cloud.shape[1]
+    if C < 3:
+        raise ValueError("pn2.provider.farthest_point_sample: needs C >= 3 (xyz), got C = %d" % C)
+    return farthest_point_sample_batch([point_cloud], number)[0]
+
+
+__all__ = ["prepare_batch", "prepare_train_batch", "draw_augmentation", "Augmentation",
+           "farthest_point_sample", "farthest_point_sample_batch"]
