@@ -28,7 +28,9 @@
  *   pn2_index_points_f32   index_points                      model/pointnet2_utils.py:28-45
  *   pn2_group_f32          grouping of sample_and_group /    model/pointnet2_utils.py:107-116,
  *                          PointNetSetAbstractionMsg         model/pointnet2_utils.py:204-209
- *   pn2_pack_layer_f32     Conv2d(1x1)+BatchNorm2d(eval) params of the shared MLP
+ *   pn2_group_backward_f32 the feature gradient of that grouping (autograd's backward of
+ *                          index_points' advanced indexing)  model/pointnet2_utils.py:44
+ *   pn2_pack_layer_f32    Conv2d(1x1)+BatchNorm2d(eval) params of the shared MLP
  *                                                            model/pointnet2_utils.py:150-156, 184-193
  *   pn2_sa_mlp_max_f32     grouped shared MLP (conv+bn+relu)* + max over the neighbourhood
  *                                                            model/pointnet2_utils.py:167-172, 211-218
@@ -87,7 +89,8 @@ const char *pn2_last_error(void);
  *                            padded with N, pointnet2_utils.py:85-89; the reference's next
  *                            index_points raises IndexError); the SA kernels read point 0 there
  *   PN2_DEVERR_INDEX         pn2_index_points_f32 / pn2_group_f32 got an index outside [-N, N)
- *                            (the element is NaN)
+ *                            (the element is NaN), or pn2_group_backward_f32 did (the position
+ *                            contributes nothing)
  * A launch raises into the slot of the device its STREAM belongs to (hipStreamGetDevice; the
  * current device for the null stream), whatever the thread's current device is.
  * pn2_error_slot_set(slot): from now on, launches by the calling thread on the current device
@@ -243,6 +246,32 @@ int pn2_group_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb,
                   int64_t sc, const float *feat, int64_t D, int64_t fb, int64_t fn, int64_t fd,
                   const float *ctr, int64_t S, const int64_t *idx, int64_t K, int feature_first,
                   float *out, void *stream);
+
+/* ---- backward of the grouping for the features (csrc/group.hip): every grouped row's feature
+ * gradient summed back into its source point, in a fixed order and without float atomics.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ *   dgrouped  [B,S,K,.] float32: row (b,s,k) starts at dgrouped[((b*S + s)*K + k) * row_stride],
+ *             its D feature columns at `offset` (0 for feature_first rows, C otherwise),
+ *             offset + D <= row_stride; read in place, 16-byte loads when D, offset, row_stride
+ *             and both bases allow them
+ *   idx       [B,S,K] int64 (PN2_INDEX_I64) or int32 (PN2_INDEX_I32), element (b,s,k) at
+ *             idx[b*ib + s*is + k*ik]
+ *   dfeat     [B,N,D] float32 contiguous, FULLY written: a point no position names gets +0.0
+ * The sum rule: dfeat[b,n,d] is the float32 sum of dgrouped[b,s,k,offset+d] over the positions
+ * with idx[b,s,k] == n, taken in ascending (s,k) order from +0.0f, one rounding per add -- what
+ * np.add.at and torch's CPU index_add_ compute, bit for bit, and the same bits on every run.
+ * Indices as pn2_group_f32: [-N, 0) counts from the end; outside [-N, N) the position
+ * contributes nothing and PN2_DEVERR_INDEX is raised.
+ * workspace: pn2_group_backward_workspace_bytes(B, N, S, K) bytes (-1: bad arguments), 4-byte
+ * aligned; the table of each point's positions is built there on every call.  S*K, B*N and D
+ * must each be below 2^31.  B == 0: nothing to do, no launch. */
+#define PN2_INDEX_I64 0
+#define PN2_INDEX_I32 1
+int64_t pn2_group_backward_workspace_bytes(int64_t B, int64_t N, int64_t S, int64_t K);
+int pn2_group_backward_f32(const float *dgrouped, int64_t row_stride, int64_t offset,
+                           const void *idx, int idx_dtype, int64_t ib, int64_t is, int64_t ik,
+                           int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, float *dfeat,
+                           void *workspace, int64_t workspace_bytes, void *stream);
 
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]

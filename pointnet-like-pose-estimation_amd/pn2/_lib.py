@@ -70,6 +70,8 @@ DEVERR_NO_NEIGHBOUR = 1
 DEVERR_INDEX = 2
 DTYPE_F32 = 0
 DTYPE_F64 = 1
+INDEX_I64 = 0
+INDEX_I32 = 1
 
 # name -> (restype, argtypes); every symbol include/pn2.h declares
 SIGNATURES = {
@@ -94,6 +96,9 @@ SIGNATURES = {
     "pn2_index_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "pn2_group_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64,
                              _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "pn2_group_backward_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "pn2_group_backward_f32": (_int, [_vp, _i64, _i64, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64,
+                                      _i64, _i64, _vp, _vp, _i64, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

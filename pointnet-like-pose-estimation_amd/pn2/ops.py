@@ -14,6 +14,8 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
   pn2::square_distance square_distance :5-26
   pn2::index_points   index_points :28-45
   pn2::group          grouping in sample_and_group :107-116 / the MSG module :204-209
+  pn2::group_backward the feature gradient of that grouping (autograd's backward of
+                      index_points :44), summed per point in position order
   pn2::pack_layer     Conv2d 1x1 + BatchNorm2d (eval) parameters :150-156, :184-193
   pn2::sa_mlp_max_    gathered shared MLP + max :167-172, :211-218 (writes into `out`)
   pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
@@ -337,6 +339,48 @@ group = torch.library.custom_op("pn2::group", group_direct, mutates_args=())
 def _(points, feature, centers, idx, feature_first):
     D = 0 if feature is None else feature.shape[2]
     return points.new_empty(points.shape[0], idx.shape[1], idx.shape[2], points.shape[2] + D)
+
+
+# ------------------------------------------------------------------------------ group_backward
+def group_backward_direct(dgrouped: Tensor, idx: Tensor, N: int, D: int, feature_first: bool) -> Tensor:
+    """The feature gradient of pn2::group: dgrouped [B,S,K,C+D] float32 (the gradient of the
+    grouped rows, read in place: any row stride, features at column 0 when feature_first, else
+    at C), idx [B,S,K] int64 or int32 (any strides) -> [B,N,D], each point the float32 sum of
+    the rows that name it, in ascending (s,k) order from +0.0 (np.add.at's bits, the same on
+    every run; pn2_group_backward_f32)."""
+    _dev(dgrouped, "pn2::group_backward")
+    if dgrouped.dtype != torch.float32 or idx.dtype not in (torch.int64, torch.int32):
+        raise TypeError("pn2::group_backward: float32 rows and int64 / int32 indices")
+    B, S, K, W = dgrouped.shape
+    if tuple(idx.shape) != (B, S, K) or not 1 <= D <= W:
+        raise ValueError("pn2::group_backward: dgrouped [B,S,K,C+D], idx [B,S,K], 1 <= D <= C+D")
+    if B * S * K == 0:  # no rows: every sum is empty
+        return torch.zeros(B, N, D, dtype=torch.float32, device=dgrouped.device)
+    rs = dgrouped.stride(2)
+    if (dgrouped.stride(3) != 1 or rs < W or dgrouped.stride(1) != K * rs or
+                      dgrouped.stride(0) != S * K * rs):
+        dgrouped = dgrouped.contiguous()  # rows that no single row stride describes
+        rs = W
+    out = torch.empty(B, N, D, dtype=torch.float32, device=dgrouped.device)
+    nbytes = int(_L.pn2_group_backward_workspace_bytes(B, N, S, K))
+    if nbytes < 0:
+        raise ValueError("pn2::group_backward: bad shape B=%d N=%d S=%d K=%d" % (B, N, S, K))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dgrouped.device)
+    ib, is_, ik = idx.stride()
+    _run("pn2_group_backward_f32", _L.pn2_group_backward_f32,
+         (dgrouped.data_ptr(), rs, 0 if feature_first else W - D, idx.data_ptr(),
+          _lib.INDEX_I32 if idx.dtype == torch.int32 else _lib.INDEX_I64, ib, is_, ik, B, N, S, K, D,
+          out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dgrouped)), dgrouped.device,
+         nbytes=4.0 * B * S * K * D + 4.0 * B * N * D)
+    return out
+
+
+group_backward = torch.library.custom_op("pn2::group_backward", group_backward_direct, mutates_args=())
+
+
+@group_backward.register_fake
+def _(dgrouped, idx, N, D, feature_first):
+    return dgrouped.new_empty(dgrouped.shape[0], N, D)
 
 
 # ------------------------------------------------------------------------------ pack_layer

@@ -33,6 +33,7 @@ import torch
 
 from . import _lib
 from . import ops
+from . import tuning
 from .ops import _stream
 
 
@@ -227,7 +228,16 @@ class _GroupTrain(torch.autograd.Function):
     the SA layers: they come from index ops of the input).  Forward: pn2_group_f32 (the same
     rows as the reference's index_points + cat, pointnet2_utils.py:107-116 / 204-209);
     backward: the feature rows' gradients added back to their source points (index_add_ --
-    atomic adds, instead of advanced indexing's sort-based backward)."""
+    atomic adds, instead of advanced indexing's sort-based backward).
+
+    The order rule.  index_add_ on the device is one float atomic add per element: the rows
+    that name a point arrive in any order, so the gradient's last bits differ from run to run
+    (the only order-dependent sum of the training step).  With tuning key group_backward=1, or
+    under torch.use_deterministic_algorithms(True) (where torch would replace index_add_ by
+    its sort-based path), the backward is pn2_group_backward_f32 instead: each point's rows
+    summed in ascending (s, k) position order from +0.0, one rounding per add -- the bits of
+    the reference's CPU backward (a sequential accumulate), the same on every run.  dgrouped is
+    read in place through its strides, the feature columns as a slice of its rows."""
 
     @staticmethod
     def forward(ctx, feature, points, centers, idx, feature_first):
@@ -239,7 +249,9 @@ class _GroupTrain(torch.autograd.Function):
     def backward(ctx, dgrouped):
         idx, = ctx.saved_tensors
         (B, N, D), C, ff = ctx.meta
-        dfeat = dgrouped[..., :D] if ff else dgrouped[..., C:]
+        if tuning.get("group_backward") == 1 or torch.are_deterministic_algorithms_enabled():
+            return ops.group_backward_direct(dgrouped, idx, N, D, ff), None, None, None, None
+        dfeat =dgrouped[..., :D] if ff else dgrouped[..., C:]
         flat = (idx + torch.arange(B, device=idx.device).view(B, 1, 1) * N).reshape(-1)
         out = torch.zeros(B * N, D, device=dgrouped.device, dtype=dgrouped.dtype)
         out.index_add_(0, flat, dfeat.reshape(-1, D))

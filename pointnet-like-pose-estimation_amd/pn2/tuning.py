@@ -28,6 +28,12 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
     eval_grad        1: an SA module's eval-mode forward under autograd runs the fused inference
                      kernels and recomputes the layer in its backward (pointnet2_utils
                      _SaEvalGrad); 0: the reference's torch formulation
+    group_backward   0: the grouping's feature gradient (train._GroupTrain.backward) by torch's
+                     index_add_ -- float atomic adds, the sum's order and last bits differ from
+                     run to run; 1: pn2_group_backward_f32, each point's rows summed in position
+                     order -- the CPU index_add_'s bits, the same on every run.  With
+                     torch.use_deterministic_algorithms(True) the kernel runs whatever the key
+                     says.  0 or 1; anything else is an error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -55,7 +61,17 @@ HOST_DEFAULTS = {
     "pipe_fuse": 1,
     "bq_multi": 1,
     "eval_grad": 1,
+    "group_backward": 0,
 }
+# host keys with a checked range (inclusive); the others take any integer
+HOST_RANGES = {"group_backward": (0, 1)}
+
+
+def _check_host(key, value):
+    lo, hi = HOST_RANGES.get(key, (value, value))
+    if not lo <= value <= hi:
+        raise ValueError("pn2 tuning: %s=%r is outside [%d, %d]" % (key, value, lo, hi))
+    return value
 
 
 def _parse(text):
@@ -70,7 +86,7 @@ def _parse(text):
 
 _ENV = _parse(os.environ.get("PN2_TUNING", ""))
 _host = dict(HOST_DEFAULTS)
-_host.update({k: v for k, v in _ENV.items() if k in HOST_DEFAULTS})
+_host.update({k: _check_host(k, v) for k, v in _ENV.items() if k in HOST_DEFAULTS})
 
 
 # Kernel keys the pipelines set while they capture / run: the FPS block of 4
@@ -165,6 +181,7 @@ def override(**kw):
     try:
         for k, v in kw.items():
             if k in HOST_DEFAULTS:
+                _check_host(k, v)
                 saved.append((k, _host[k], True))
                 _host[k] = v
             else:
