@@ -34,6 +34,10 @@
  *                                                            model/pointnet2_utils.py:150-156, 184-193
  *   pn2_sa_mlp_max_f32     grouped shared MLP (conv+bn+relu)* + max over the neighbourhood
  *                                                            model/pointnet2_utils.py:167-172, 211-218
+ *   pn2_gemm_nt_f32 / pn2_gemm_nn_f32 / pn2_gemm_tn_f32
+ *                          the shared MLP's 1x1 convs under autograd: forward, input gradient,
+ *                          weight gradient, each sum in a fixed order
+ *                                                            model/pointnet2_utils.py:167-172, 211-218
  *   pn2_bn_train_stats_f32 / pn2_bn_relu_apply_f32 (/ pn2_bn_train_forward_f32: both) /
  *   pn2_group_max_f32 / pn2_bn_relu_backward_f32
  *                          train-mode BatchNorm2d + ReLU + torch.max over K, forward and backward
@@ -272,6 +276,46 @@ int pn2_group_backward_f32(const float *dgrouped, int64_t row_stride, int64_t of
                            const void *idx, int idx_dtype, int64_t ib, int64_t is, int64_t ik,
                            int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, float *dfeat,
                            void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- the three matrix products of a shared-MLP layer's training step (csrc/train_gemm.hip),
+ * every sum in a fixed, documented order: no float atomics, no workgroup waits on another.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * All operands float32 row-major with a leading dimension (>= the matrix width), read and
+ * written in place through it; no load ever passes the end of a row, 16-byte loads only where
+ * base and leading dimension allow them.  Arithmetic: each operand value in three bf16 planes,
+ * six v_mfma_f32_32x32x16_bf16 per product step (csrc/split_bf16.h): fp32-GEMM accuracy.
+ *   pn2_gemm_nt_f32  C[M,N] = A[M,K] B[N,K]^T (+ bias[N]; bias may be NULL)    Y  = X W^T + b
+ *   pn2_gemm_nn_f32  C[M,N] = A[M,K] B[K,N]   (B as stored: no transpose copy) dX = dY W
+ *   pn2_gemm_tn_f32  C[N,K] = A[M,N]^T B[M,K] (the sum over the M rows)        dW = dY^T X
+ * Order of nt and nn: an element's accumulator starts at +0 and takes the reduction dimension
+ * in ascending 16-wide steps (zero-padded past its end); the bias is added once, at the end.
+ * ROW INDEPENDENCE of nt and nn: row r of C is a function of row r of A, of B and of the bias
+ * only -- not of M, not of the row's position: the reduction is never split by anything that
+ * depends on M.
+ * THE ORDER RULE of tn:
+ *   1. the rows are cut into slabs of R = pn2_gemm_tn_slab_rows() rows (a compile-time constant,
+ *      a multiple of 32): slab j holds rows [j*R, min((j+1)*R, M));
+ *   2. slab j's partial P_j is a float32 [N,K] matrix that depends only on that slab's rows
+ *      -- not on j, M, the device's CU count or what else runs: it is, bit for bit, what this
+ *      entry returns when called on that slab alone (inside a slab: ascending 16-row steps
+ *      from +0, fixed);
+ *   3. C = float32(sum_j double(P_j)), added in ascending j from +0.0 in float64, rounded once.
+ *   One launch writes the partials to `workspace`, a second one reduces them; M <= R takes the
+ *   same two steps.  workspace: pn2_gemm_tn_workspace_bytes(M, N, K) = ceil(M/R) * N * K * 4
+ *   bytes exactly (-1: bad arguments), 4-byte aligned.
+ * Limits: 1 <= N, K <= 4096 (above: PN2_EUNSUPPORTED); M >= 0; M == 0 returns PN2_OK, launches
+ * nothing and writes nothing (also for tn, whose C would be all zero).  Violations are reported
+ * before any device call.  Non-finite inputs: the outputs that depend on one are non-finite
+ * (Inf or NaN: the split of an Inf has a NaN residual), all others are unaffected. */
+int pn2_gemm_nt_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias,
+                    float *C, int64_t ldc, int64_t M, int64_t N, int64_t K, void *stream);
+int pn2_gemm_nn_f32(const float *A, int64_t lda, const float *B, int64_t ldb, float *C,
+                    int64_t ldc, int64_t M, int64_t N, int64_t K, void *stream);
+int64_t pn2_gemm_tn_slab_rows(void);
+int64_t pn2_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int pn2_gemm_tn_f32(const float *A, int64_t lda, const float *B, int64_t ldb, float *C,
+                    int64_t ldc, int64_t M, int64_t N, int64_t K, void *workspace,
+                    int64_t workspace_bytes, void *stream);
 
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]

@@ -99,6 +99,11 @@ SIGNATURES = {
     "pn2_group_backward_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "pn2_group_backward_f32": (_int, [_vp, _i64, _i64, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64,
                                       _i64, _i64, _vp, _vp, _i64, _vp]),
+    "pn2_gemm_nt_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "pn2_gemm_nn_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "pn2_gemm_tn_slab_rows": (_i64, []),
+    "pn2_gemm_tn_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "pn2_gemm_tn_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

@@ -16,6 +16,8 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
   pn2::group          grouping in sample_and_group :107-116 / the MSG module :204-209
   pn2::group_backward the feature gradient of that grouping (autograd's backward of
                       index_points :44), summed per point in position order
+  pn2::gemm_nt / gemm_nn / gemm_tn  the shared MLP's 1x1 convs under autograd :167-172 (forward,
+                      input gradient, weight gradient), every sum in a fixed order
   pn2::pack_layer     Conv2d 1x1 + BatchNorm2d (eval) parameters :150-156, :184-193
   pn2::sa_mlp_max_    gathered shared MLP + max :167-172, :211-218 (writes into `out`)
   pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
@@ -381,6 +383,123 @@ group_backward = torch.library.custom_op("pn2::group_backward", group_backward_d
 @group_backward.register_fake
 def _(dgrouped, idx, N, D, feature_first):
     return dgrouped.new_empty(dgrouped.shape[0], N, D)
+
+
+# ------------------------------------------------------------------------------ training GEMMs
+def _matrix(t: Tensor, what: str) -> Tuple[Tensor, int]:
+    """A 2-D float32 device matrix as the GEMM kernels read it in place -> (tensor, leading
+    dimension): unit column stride and a row stride >= the width (a slice of wider rows is
+    fine); any other view is copied."""
+    _dev(t, what)
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError("%s: 2-D float32 matrices" % what)
+    rows, width = t.shape
+    if rows <= 1 and (width <= 1 or t.stride(1) == 1):
+        return t, max(width, 1)  # a single row: its stride is never used
+    if t.stride(1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    return t, max(t.stride(0), 1)
+
+
+_GEMM_WS = {}
+
+
+def _gemm_workspace(nbytes: int, device, stream: int) -> Tensor:
+    """pn2_gemm_tn_f32's slab partials: one grow-only buffer per (device, stream) -- every use
+    is ordered on that stream."""
+    key = (device, stream)
+    ws = _GEMM_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+        _GEMM_WS[key] = ws
+    return ws
+
+
+def gemm_nt_direct(A: Tensor, B: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """A [M,K], B [N,K], bias [N] or None -> A B^T + bias [M,N] (pn2_gemm_nt_f32: each row of
+    the result a function of that row of A, of B and of the bias only; ascending 16-wide steps
+    over K from +0, the bias added last).  Operands are read in place through their row stride."""
+    A, lda = _matrix(A, "pn2::gemm_nt")
+    B, ldb = _matrix(B, "pn2::gemm_nt")
+    M, K = A.shape
+    N = B.shape[0]
+    if B.shape[1] != K or B.device != A.device:
+        raise ValueError("pn2::gemm_nt: A [M,K], B [N,K] on one device")
+    bp = 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (N,) or bias.device != A.device:
+            raise ValueError("pn2::gemm_nt: bias [N] float32 on A's device")
+        bias = bias.contiguous()
+        bp = bias.data_ptr()
+    C = torch.empty(M, N, dtype=torch.float32, device=A.device)
+    _run("pn2_gemm_nt_f32", _L.pn2_gemm_nt_f32,
+         (A.data_ptr(), lda, B.data_ptr(), ldb, bp, C.data_ptr(), N, M, N, K, _stream(A)), A.device,
+         flops=2.0 * M * N * K, nbytes=4.0 * (M * K + N * K + M * N))
+    return C
+
+
+gemm_nt = torch.library.custom_op("pn2::gemm_nt", gemm_nt_direct, mutates_args=())
+
+
+@gemm_nt.register_fake
+def _(A, B, bias):
+    return A.new_empty(A.shape[0], B.shape[0])
+
+
+def gemm_nn_direct(A: Tensor, B: Tensor) -> Tensor:
+    """A [M,K], B [K,N] -> A B [M,N] (pn2_gemm_nn_f32: B read as stored, row independence and
+    order as gemm_nt)."""
+    A, lda = _matrix(A, "pn2::gemm_nn")
+    B, ldb = _matrix(B, "pn2::gemm_nn")
+    M, K = A.shape
+    N = B.shape[1]
+    if B.shape[0] != K or B.device != A.device:
+        raise ValueError("pn2::gemm_nn: A [M,K], B [K,N] on one device")
+    C = torch.empty(M, N, dtype=torch.float32, device=A.device)
+    _run("pn2_gemm_nn_f32", _L.pn2_gemm_nn_f32,
+         (A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), N, M, N, K, _stream(A)), A.device,
+         flops=2.0 * M * N * K, nbytes=4.0 * (M * K + N * K + M * N))
+    return C
+
+
+gemm_nn = torch.library.custom_op("pn2::gemm_nn", gemm_nn_direct, mutates_args=())
+
+
+@gemm_nn.register_fake
+def _(A, B):
+    return A.new_empty(A.shape[0], B.shape[1])
+
+
+def gemm_tn_direct(A: Tensor, B: Tensor) -> Tensor:
+    """A [M,N], B [M,K] -> A^T B [N,K], the sum over the M rows (pn2_gemm_tn_f32: float32
+    partials of pn2_gemm_tn_slab_rows()-row slabs, added in slab order in float64 and rounded
+    once; the same bits on every run).  M == 0 gives zeros."""
+    A, lda = _matrix(A, "pn2::gemm_tn")
+    B, ldb = _matrix(B, "pn2::gemm_tn")
+    M, N = A.shape
+    K = B.shape[1]
+    if B.shape[0] != M or B.device != A.device:
+        raise ValueError("pn2::gemm_tn: A [M,N], B [M,K] on one device")
+    if M == 0:
+        return torch.zeros(N, K, dtype=torch.float32, device=A.device)
+    nbytes = int(_L.pn2_gemm_tn_workspace_bytes(M, N, K))
+    if nbytes < 0:
+        raise ValueError("pn2::gemm_tn: bad shape M=%d N=%d K=%d" % (M, N, K))
+    st = _stream(A)
+    ws = _gemm_workspace(nbytes, A.device, st)
+    C = torch.empty(N, K, dtype=torch.float32, device=A.device)
+    _run("pn2_gemm_tn_f32", _L.pn2_gemm_tn_f32,
+         (A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), K, M, N, K, ws.data_ptr(), ws.numel(), st),
+         A.device, flops=2.0 * M * N * K, nbytes=4.0 * (M * N + M * K + N * K) + 2.0 * nbytes)
+    return C
+
+
+gemm_tn = torch.library.custom_op("pn2::gemm_tn", gemm_tn_direct, mutates_args=())
+
+
+@gemm_tn.register_fake
+def _(A, B):
+    return A.new_empty(A.shape[1], B.shape[1])
 
 
 # ------------------------------------------------------------------------------ pack_layer

@@ -7,7 +7,10 @@ BatchNorm2d with batch statistics over all B*S*K rows, ReLU, torch.max over K.
 
 Here the rows stay channels-last [M = B*S*K, C] (the grouping's natural layout -- no [B,C,K,S]
 permute copies).  The three GEMMs of each layer (Y = X W^T + b, dW = dY^T X, dX = dY W) are plain
-library GEMMs (torch.mm -> hipBLASLt); the batch-statistics BatchNorm, ReLU, running-stat update,
+library GEMMs (torch.mm -> hipBLASLt) by default; with tuning key train_gemm=1 they are the HIP
+kernels of csrc/train_gemm.hip (pn2_gemm_nt_f32 / pn2_gemm_nn_f32 / pn2_gemm_tn_f32: split-bf16
+products at fp32 accuracy, every sum in a fixed order -- include/pn2.h), so that a layer's step
+runs no library arithmetic.  The batch-statistics BatchNorm, ReLU, running-stat update,
 max + argmax and their backward are the fused HIP kernels of csrc/train.hip (one pass over the
 activations each).  BatchNorm semantics follow torch's train mode: biased variance normalises,
 running_var takes the unbiased one, momentum None = cumulative average, num_batches_tracked += 1.
@@ -124,13 +127,17 @@ class _MlpMaxTrain(torch.autograd.Function):
         n = len(cfg)
         M = x0.shape[0]
         st = _stream(x0)
+        fixed = ctx.fixed = tuning.get("train_gemm") == 1  # the backward takes the forward's route
         xs, ys, stats = [x0], [], []
         x, pooled = x0, None
         for l in range(n):
             W, b, g, be = params[4 * l:4 * l + 4]
             eps, mom, rm, rv, flags = cfg[l]
             cout = W.shape[0]
-            Y = torch.addmm(b, x, W.reshape(cout, -1).t())
+            if fixed:
+                Y = ops.gemm_nt_direct(x, W.reshape(cout, -1), b)
+            else:
+                Y = torch.addmm(b, x, W.reshape(cout, -1).t())
             if flags & _lib.LAYER_FROZEN_STATS:
                 mean, invstd = rm, torch.rsqrt(rv + eps)
                 ys.append(Y)
@@ -214,12 +221,12 @@ class _MlpMaxTrain(torch.autograd.Function):
                 "pn2_bn_relu_backward_f32")
             X = xs[l]
             W2 = W.reshape(cout, -1)
-            grads[4 * l] = _grad_weight(dY, X).view_as(W)
+            grads[4 * l] = (ops.gemm_tn_direct(dY, X) if ctx.fixed else _grad_weight(dY, X)).view_as(W)
             grads[4 * l + 1] = dbias  # sum_r dY, from the BN sums (no extra pass over dY)
             grads[4 * l + 2] = dgamma
             grads[4 * l + 3] = dbeta
             if l > 0 or ctx.needs_input_grad[0]:
-                dA = torch.mm(dY, W2)
+                dA = ops.gemm_nn_direct(dY, W2) if ctx.fixed else torch.mm(dY, W2)
         return (dA if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 

@@ -34,6 +34,13 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      order -- the CPU index_add_'s bits, the same on every run.  With
                      torch.use_deterministic_algorithms(True) the kernel runs whatever the key
                      says.  0 or 1; anything else is an error
+    train_gemm       0: the three matrix products of a shared-MLP layer's training step
+                     (train._MlpMaxTrain: Y = X W^T + b, dX = dY W, dW = dY^T X) are library
+                     GEMMs (torch.addmm / mm / bmm), whose summation order is the library's
+                     choice; 1: pn2_gemm_nt_f32 / pn2_gemm_nn_f32 / pn2_gemm_tn_f32, every sum
+                     in a fixed order (include/pn2.h) -- with group_backward=1 an SA layer's
+                     step then has no order-dependent sum.  Not tied to
+                     torch.use_deterministic_algorithms.  0 or 1; anything else is an error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -62,9 +69,10 @@ HOST_DEFAULTS = {
     "bq_multi": 1,
     "eval_grad": 1,
     "group_backward": 0,
+    "train_gemm": 0,
 }
 # host keys with a checked range (inclusive); the others take any integer
-HOST_RANGES = {"group_backward": (0, 1)}
+HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1)}
 
 
 def _check_host(key, value):

@@ -11,7 +11,8 @@ csrc = os.path.dirname(os.path.abspath(src))
 flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(csrc, "../../include"),
          "-I" + csrc, "-c", src, "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage",
          "--offload-device-only"]
-if os.path.basename(src) not in ("sa_mlp.hip", "sa_chain.hip", "sa_dense.hip", "linear.hip"):
+if os.path.basename(src) not in ("sa_mlp.hip", "sa_chain.hip", "sa_dense.hip", "linear.hip",
+                                 "train_gemm.hip"):
     flags.append("-ffp-contract=off")
 if os.path.basename(src) == "sa_dense.hip":  # csrc/Makefile DENSEFLAGS
     flags += ["-mllvm", "-amdgpu-mfma-vgpr-form"]
