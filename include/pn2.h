@@ -38,6 +38,10 @@
  *                          the shared MLP's 1x1 convs under autograd: forward, input gradient,
  *                          weight gradient, each sum in a fixed order
  *                                                            model/pointnet2_utils.py:167-172, 211-218
+ *   pn2_fc_bn_forward_f32 / pn2_fc_bn_backward_f32
+ *                          the heads' Linear + BatchNorm1d + ReLU under autograd, forward and
+ *                          backward, each sum in a fixed order   model/pointnet2_cls_ssg.py:31-36;
+ *                                                            translation_ssg.py:23-26
  *   pn2_bn_train_stats_f32 / pn2_bn_relu_apply_f32 (/ pn2_bn_train_forward_f32: both) /
  *   pn2_group_max_f32 / pn2_bn_relu_backward_f32
  *                          train-mode BatchNorm2d + ReLU + torch.max over K, forward and backward
@@ -316,6 +320,71 @@ int64_t pn2_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int pn2_gemm_tn_f32(const float *A, int64_t lda, const float *B, int64_t ldb, float *C,
                     int64_t ldc, int64_t M, int64_t N, int64_t K, void *workspace,
                     int64_t workspace_bytes, void *stream);
+
+/* ---- a heads' fully connected layer under autograd, one launch each way (csrc/fc_train.hip):
+ * Linear + BatchNorm1d (batch or running statistics) + ReLU forward, and its backward up to dY,
+ * dW and the parameter gradients, for batches that fit one workgroup.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * Reference: fc1/bn1/relu, fc2/bn2/relu, fc3 under the training loops' autograd,
+ * model/pointnet2_cls_ssg.py:31-36, rotation_ssg.py:33-37, translation_ssg.py:23-26,
+ * pointnet_utils.py:33-40.
+ * All matrices float32 row-major with a leading dimension (>= the width), read and written in
+ * place through it; 16-byte loads only where base and leading dimension allow, no load past an
+ * edge.  Plain float32 FMA arithmetic.  B <= pn2_fc_train_max_rows() (a compile-time constant,
+ * >= 64); a workgroup owns 4 output columns and all B rows of them.
+ *
+ * pn2_fc_bn_forward_f32: X [B][K], W [N][K], bias [N] -> Y [B][N] = X W^T + bias (always
+ *   written: the backward reads it), A [B][N] = act(bn(Y)), flags PN2_LAYER_*:
+ *   gamma != NULL, no PN2_LAYER_FROZEN_STATS: batch statistics.  Per column s = sum_r Y,
+ *     q = sum_r Y*Y in float64, mean = s/B, var = max(q/B - mean^2, 0), invstd =
+ *     1/sqrt(var + eps); stats = [float32(mean) | float32(invstd)] (2N floats);
+ *     A = act((Y - mean)*invstd*gamma + beta) with the rounded statistics (float32 operations,
+ *     each rounded on its own).  momentum > 0: running_mean/var = (1-momentum)*old + momentum*
+ *     (mean, var*B/(B-1)) in float64 (torch's rule; pn2_bn_train_stats_f32's); momentum <= 0:
+ *     the running statistics are neither read nor written and may be NULL.  B == 1: PN2_EINVAL.
+ *   gamma != NULL, PN2_LAYER_FROZEN_STATS: mean = running_mean, invstd = float32(1/sqrt(
+ *     double(running_var) + eps)), both only read; stats receives them.
+ *   gamma == NULL: no BatchNorm, A = act(Y); stats, beta and the running statistics are not
+ *     touched and may be NULL.
+ *   act is the ReLU (x > 0 ? x : 0), the identity with PN2_LAYER_NO_RELU.
+ * pn2_fc_bn_backward_f32: dA [B][N], the forward's Y, X and stats (and gamma, beta: the same
+ *   pointers-or-NULL and the same flags as the forward) ->
+ *     dXn = dA * [A > 0], A recomputed from Y and stats by the forward's expression (dA itself
+ *       with PN2_LAYER_NO_RELU);
+ *     dbeta[N] = float32(sum_r dXn), dgamma[N] = float32(sum_r dXn * xhat), float64 sums of
+ *       float64 products, xhat = (Y - mean)*invstd in float64 inside the sum;
+ *     dY [B][N] = gamma*invstd*(dXn - dbeta/B - xhat*dgamma/B) (batch statistics; float32,
+ *       the two means rounded to float32 first), gamma*invstd*dXn (frozen), dXn (no BN);
+ *     dbias[N] = float32(sum_r double(dY));  dW [N][K] = sum_r dY[r][n] * X[r][k].
+ *   dX is not computed here: it is pn2_gemm_nn_f32(dY, W).  dgamma / dbeta may be NULL (and
+ *   are not written) when gamma is NULL.
+ * THE ORDER RULES:
+ *   1. An element of Y is one chain acc = fma(X[r][k], W[n][k], acc) (a single rounding per
+ *      step) over k = 0, 1, .. K-1 from +0, then one float32 add of bias[n].  The order
+ *      depends on K alone: not on B, N, the row's or column's position or a leading dimension.
+ *      ROW INDEPENDENCE: row r of Y is a function of row r of X, of W and of the bias only.
+ *   2. Every column sum over the rows (s, q, dbeta, dgamma, dbias) is a float64 sum in
+ *      ascending row order r = 0 .. B-1 from +0.0.  An element of dW is acc = fma(dY[r][n],
+ *      X[r][k], acc) in float32 over r = 0 .. B-1 from +0.0f: an fma, one rounding per step
+ *      (the unit is compiled without contraction; an fma is only where the source asks).
+ *   3. No float atomics.
+ *   4. No workgroup waits for, or reads, another's result; no workspace.
+ * Errors, before any device call: PN2_EINVAL for B < 1, N < 1, K < 1, a leading dimension below
+ * its width, a NULL required pointer, gamma without beta / stats (/ dgamma / dbeta), unknown
+ * flags, batch statistics with B == 1; PN2_EUNSUPPORTED for B > pn2_fc_train_max_rows(). */
+int64_t pn2_fc_train_max_rows(void);
+int pn2_fc_bn_forward_f32(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias,
+                          int64_t B, int64_t N, int64_t K, double eps, double momentum,
+                          float *running_mean, float *running_var,
+                          const float *gamma, const float *beta,
+                          float *Y, int64_t ldy, float *A, int64_t lda,
+                          float *stats /* [mean | invstd], 2N */, int flags, void *stream);
+int pn2_fc_bn_backward_f32(const float *dA, int64_t ldd, const float *Y, int64_t ldy,
+                           const float *X, int64_t ldx, const float *stats,
+                           const float *gamma, const float *beta,
+                           int64_t B, int64_t N, int64_t K,
+                           float *dY, int64_t ldyy, float *dW, int64_t ldw, float *dbias,
+                           float *dgamma, float *dbeta, int flags, void *stream);
 
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]

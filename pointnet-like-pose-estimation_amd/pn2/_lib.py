@@ -104,6 +104,11 @@ SIGNATURES = {
     "pn2_gemm_tn_slab_rows": (_i64, []),
     "pn2_gemm_tn_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "pn2_gemm_tn_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pn2_fc_train_max_rows": (_i64, []),
+    "pn2_fc_bn_forward_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _dbl, _dbl, _vp, _vp,
+                                     _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp]),
+    "pn2_fc_bn_backward_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
+                                      _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

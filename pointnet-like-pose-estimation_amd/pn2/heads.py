@@ -29,13 +29,17 @@ from . import geometry
 from . import ops
 from . import tuning
 from .pointnet_utils import _fold_linear, linear_bn
+from .train import linear_bn_train
 
 
 class _FCHead(nn.Module):
     """fc1/bn1/relu/drop -> fc2/bn2/relu/drop -> fc3, shared by every head.  Eval without
     autograd: each fc + bn folded into one (W', b') and the whole tail in three launches
     (pn2.ops.fc_tail: fc1 and fc2 as row kernels, then fc3 fused with the classifiers'
-    log_softmax and argmax; dropout is the identity in eval).  Otherwise, or when a layer cannot fold, the reference's modules."""
+    log_softmax and argmax; dropout is the identity in eval).  Otherwise, or when a layer cannot fold, the reference's modules;
+    with tuning key train_head=1 each fc (+ bn + relu) under autograd is one launch of
+    csrc/fc_train.hip forward and one backward (pn2.train.linear_bn_train), dropout the module's
+    own call between them."""
 
     def _folded(self):
         c = self._fc_cache
@@ -57,6 +61,10 @@ class _FCHead(nn.Module):
             x = linear_bn(x, self.fc1, self.bn1, self._fc_cache.setdefault(1, {}))
             x = linear_bn(x, self.fc2, self.bn2, self._fc_cache.setdefault(2, {}))
             return linear_bn(x, self.fc3, None, self._fc_cache.setdefault(3, {}), relu=False)
+        if tuning.get("train_head") == 1:  # the fc_train kernels; dropout stays the module's
+            x = self.drop(linear_bn_train(x, self.fc1, self.bn1))
+            x = self.drop(linear_bn_train(x, self.fc2, self.bn2))
+            return linear_bn_train(x, self.fc3, None, relu=False)
         x = self.drop(F.relu(self.bn1(self.fc1(x))))
         x = self.drop(F.relu(self.bn2(self.fc2(x))))
         return self.fc3(x)
@@ -70,6 +78,9 @@ class _FCHead(nn.Module):
             c = self._fc_cache
             h = linear_bn(mean, self.mean_fc1, self.mean_bn1, c.setdefault("mean1", {}))
             return linear_bn(h, self.mean_fc2, None, c.setdefault("mean2", {}), relu=False)
+        if tuning.get("train_head") == 1:
+            h = linear_bn_train(mean, self.mean_fc1, self.mean_bn1)
+            return linear_bn_train(h, self.mean_fc2, None, relu=False)
         return self.mean_fc2(F.relu(self.mean_bn1(self.mean_fc1(mean))))
 
     def _fc_log_softmax(self, x):

@@ -21,7 +21,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import tuning
 from .pointnet2_utils import _needs_autograd
+from .train import linear_bn_train
 from .pointnet_utils import (PointNetEncoder, TNet3d, TNetkd, _rows_to_cf, linear_bn, mlp_mode,
                              run_mlp)
 
@@ -73,6 +75,13 @@ class _ConvStack(nn.Module):
             for i in range(n):
                 x = linear_bn(x, self.fc[i], self.bn_fc[i] if i < n - 1 else None,
                               self._fc_cache.setdefault(i, {}), relu=i < n - 1)
+            return x
+        if tuning.get("train_head") == 1:  # fc + bn_fc on the fc_train kernels; dropout and the
+            for i in range(len(self.fc)):  # ReLU after it stay torch (elementwise)
+                if i < len(self.fc) - 1:
+                    x = F.relu(self.dropout(linear_bn_train(x, self.fc[i], self.bn_fc[i], relu=False)))
+                else:
+                    x = linear_bn_train(x, self.fc[i], None, relu=False)
             return x
         for i in range(len(self.fc)):
             if i < len(self.fc) - 1:

@@ -502,6 +502,88 @@ def _(A, B):
     return A.new_empty(A.shape[1], B.shape[1])
 
 
+# ------------------------------------------------------------------------------ FC heads, training
+def fc_train_max_rows() -> int:
+    """The largest batch pn2_fc_bn_forward_f32 / pn2_fc_bn_backward_f32 accept."""
+    return int(_L.pn2_fc_train_max_rows())
+
+
+def _vector(t: Optional[Tensor], n: int, what: str, like: Tensor) -> int:
+    if t is None:
+        return 0
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != like.device or not t.is_contiguous():
+        raise ValueError("%s: contiguous float32 [%d] vectors on the input's device" % (what, n))
+    return t.data_ptr()
+
+
+def fc_bn_forward_direct(x: Tensor, weight: Tensor, bias: Tensor, gamma: Optional[Tensor],
+                         beta: Optional[Tensor], running_mean: Optional[Tensor],
+                         running_var: Optional[Tensor], eps: float, momentum: float, relu: bool,
+                         frozen: bool) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """x [B,K], weight [N,K], bias [N] -> (Y = x W^T + b, A = act(bn(Y)), stats [mean | invstd]
+    or None without BN), one launch (pn2_fc_bn_forward_f32; include/pn2.h states the order
+    rules).  gamma None: no BatchNorm.  frozen: the running statistics normalise and are only
+    read; else batch statistics, and momentum > 0 updates running_mean / running_var in place.
+    Strided 2-D views with unit column stride are read in place."""
+    what = "pn2::fc_bn_forward"
+    x, ldx = _matrix(x, what)
+    weight, ldw = _matrix(weight, what)
+    B, K = x.shape
+    N = weight.shape[0]
+    if weight.shape[1] != K or weight.device != x.device:
+        raise ValueError("%s: x [B,K], weight [N,K] on one device" % what)
+    if gamma is not None and not frozen and B == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                         % (torch.Size([B, N]),))
+    upd = gamma is not None and not frozen and momentum > 0.0
+    use_running = frozen or upd
+    Y = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    A = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    stats = torch.empty(2 * N, dtype=torch.float32, device=x.device) if gamma is not None else None
+    flags = (0 if relu else _lib.LAYER_NO_RELU) | (_lib.LAYER_FROZEN_STATS if frozen and gamma is not None else 0)
+    _run("pn2_fc_bn_forward_f32", _L.pn2_fc_bn_forward_f32,
+         (x.data_ptr(), ldx, weight.data_ptr(), ldw, _vector(bias, N, what, x), B, N, K, float(eps),
+          float(momentum) if upd else 0.0,
+          _vector(running_mean if use_running else None, N, what, x),
+          _vector(running_var if use_running else None, N, what, x),
+          _vector(gamma, N, what, x), _vector(beta if gamma is not None else None, N, what, x),
+          Y.data_ptr(), N, A.data_ptr(), N, 0 if stats is None else stats.data_ptr(), flags, _stream(x)),
+         x.device, flops=2.0 * B * N * K, nbytes=4.0 * (B * K + N * K + 2 * B * N))
+    return Y, A, stats
+
+
+def fc_bn_backward_direct(dA: Tensor, Y: Tensor, x: Tensor, stats: Optional[Tensor],
+                          gamma: Optional[Tensor], beta: Optional[Tensor], relu: bool, frozen: bool):
+    """The backward of fc_bn_forward_direct up to the layer's own gradients
+    (pn2_fc_bn_backward_f32) -> (dY [B,N], dW [N,K], dbias [N], dgamma, dbeta -- None without
+    BN).  The input gradient is gemm_nn_direct(dY, weight)."""
+    what = "pn2::fc_bn_backward"
+    dA, ldd = _matrix(dA, what)
+    Y, ldy = _matrix(Y, what)
+    x, ldx = _matrix(x, what)
+    B, N = Y.shape
+    K = x.shape[1]
+    if tuple(dA.shape) != (B, N) or x.shape[0] != B or dA.device != x.device or Y.device != x.device:
+        raise ValueError("%s: dA [B,N], Y [B,N], x [B,K] on one device" % what)
+    bn = gamma is not None
+    if bn and (stats is None or stats.dtype != torch.float32 or stats.numel() != 2 * N or
+               not stats.is_contiguous() or stats.device != x.device):
+        raise ValueError("%s: stats is the forward's [mean | invstd], 2N float32" % what)
+    dY = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    dW = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    dbias = torch.empty(N, dtype=torch.float32, device=x.device)
+    dgamma = torch.empty(N, dtype=torch.float32, device=x.device) if bn else None
+    dbeta = torch.empty(N, dtype=torch.float32, device=x.device) if bn else None
+    flags = (0 if relu else _lib.LAYER_NO_RELU) | (_lib.LAYER_FROZEN_STATS if frozen and bn else 0)
+    _run("pn2_fc_bn_backward_f32", _L.pn2_fc_bn_backward_f32,
+         (dA.data_ptr(), ldd, Y.data_ptr(), ldy, x.data_ptr(), ldx, stats.data_ptr() if bn else 0,
+          _vector(gamma, N, what, x), _vector(beta if bn else None, N, what, x), B, N, K,
+          dY.data_ptr(), N, dW.data_ptr(), K, dbias.data_ptr(), dgamma.data_ptr() if bn else 0,
+          dbeta.data_ptr() if bn else 0, flags, _stream(x)),
+         x.device, flops=2.0 * B * N * K, nbytes=4.0 * (B * K + N * K + 3 * B * N))
+    return dY, dW, dbias, dgamma, dbeta
+
+
 # ------------------------------------------------------------------------------ pack_layer
 def pack_layer_direct(weight: Tensor, bias: Optional[Tensor], gamma: Optional[Tensor],
                beta: Optional[Tensor], mean: Optional[Tensor], var: Optional[Tensor],

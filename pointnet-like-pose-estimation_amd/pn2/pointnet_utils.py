@@ -21,7 +21,10 @@ The small per-cloud transforms (torch.bmm of a 3x3 / 64x64 matrix with the point
 T-Nets' FC layers are plain library GEMMs (torch on the GPU).  Training on the GPU runs the same
 shared MLPs through pn2.train.point_mlp_train (library GEMMs + the fused batch-statistics BN /
 ReLU / max kernels, forward and backward) in the same rows layout; eval with autograd (and
-exotic BN configurations) keeps the reference's torch formulation.
+exotic BN configurations) keeps the reference's torch formulation.  With tuning key
+train_head=1 the T-Nets' FC tail under autograd (fc1/bn4, fc2/bn5, fc3) runs on the kernels of
+csrc/fc_train.hip (pn2.train.linear_bn_train); the ``+ iden`` stays a torch add and the bmm
+transforms stay library calls.
 """
 import numpy as np
 import torch
@@ -31,6 +34,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import ops
 from . import train
+from . import tuning
 from .pointnet2_utils import _needs_autograd, _precision
 
 
@@ -226,9 +230,14 @@ class _TNet(nn.Module):
             g = linear_bn(g, self.fc2, self.bn5, self._fc_cache.setdefault(2, {}))
             g = linear_bn(g, self.fc3, None, self._fc_cache.setdefault(3, {}), relu=False, extra=self._iden)
             return g.view(-1, self._k, self._k)
-        g = F.relu(self.bn4(self.fc1(g)))
-        g = F.relu(self.bn5(self.fc2(g)))
-        g = self.fc3(g)
+        if tuning.get("train_head") == 1:  # the fc_train kernels
+            g = train.linear_bn_train(g, self.fc1, self.bn4)
+            g = train.linear_bn_train(g, self.fc2, self.bn5)
+            g = train.linear_bn_train(g, self.fc3, None, relu=False)
+        else:
+            g = F.relu(self.bn4(self.fc1(g)))
+            g = F.relu(self.bn5(self.fc2(g)))
+            g = self.fc3(g)
         g = g + self._iden.expand(B, -1)
         return g.view(-1, self._k, self._k)
 

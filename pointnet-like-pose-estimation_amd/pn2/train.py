@@ -31,8 +31,15 @@ last layer runs pn2_bn_relu_group_max_f32, which keeps Y and never writes its ac
 SA modules' eval-mode forward under autograd recomputes a layer with it in its backward
 (pn2/pointnet2_utils.py); the v1 modules' eval forward with autograd keeps the reference's
 torch formulation.
+
+The heads' FC layers (linear_bn_train, tuning key train_head=1): Linear + BatchNorm1d + ReLU of
+the FC tails, the translation heads' mean MLP and the T-Nets' tail under autograd, in train mode
+(batch statistics) and in eval mode (frozen), one launch forward and one backward
+(csrc/fc_train.hip: the whole batch inside one workgroup, float64 column sums in row order),
+plus pn2_gemm_nn_f32 for the input gradient.
 """
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 from . import ops
@@ -333,5 +340,67 @@ def point_mlp_train(x, convs, bns, rows, pool=True, last_relu=True):
     return out if pool else out.view(B, N, -1)
 
 
+class _FcBnTrain(torch.autograd.Function):
+    """One FC layer of a head under autograd: Linear (+ BatchNorm1d with batch or frozen
+    statistics) (+ ReLU) as pn2_fc_bn_forward_f32, its backward as pn2_fc_bn_backward_f32 plus
+    pn2_gemm_nn_f32 for the input gradient -- every sum in a fixed order (include/pn2.h).
+    Saved for the backward: x, Y, stats and the parameters, nothing else (A is recomputed)."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, W, b, g, be):
+        """cfg = (eps, momentum factor, running_mean, running_var, relu, frozen); g / be None:
+        no BatchNorm."""
+        eps, mom, rm, rv, relu, frozen = cfg
+        Y, A, stats = ops.fc_bn_forward_direct(x, W, b, g, be, rm, rv, eps, mom, relu, frozen)
+        ctx.relu, ctx.frozen, ctx.bn = relu, frozen, g is not None
+        if ctx.bn:
+            ctx.save_for_backward(x, Y, W, stats, g, be)
+        else:
+            ctx.save_for_backward(x, Y, W)
+        return A
+
+    @staticmethod
+    def backward(ctx, dA):
+        if ctx.bn:
+            x, Y, W, stats, g, be = ctx.saved_tensors
+        else:
+            (x, Y, W), stats, g, be = ctx.saved_tensors, None, None, None
+        dY, dW, db, dg, dbe = ops.fc_bn_backward_direct(dA, Y, x, stats, g, be, ctx.relu, ctx.frozen)
+        dx = ops.gemm_nn_direct(dY, W) if ctx.needs_input_grad[0] else None
+        return dx, None, dW, db, dg, dbe
+
+
+def linear_bn_train(x, fc, bn, relu=True):
+    """act(bn(fc(x))) for a head's FC layer under autograd -- ``F.relu(bn(fc(x)))`` of the
+    reference's tails (pointnet2_cls_ssg.py:32-35), ``fc(x)`` alone with bn=None, relu=False --
+    on the kernels of csrc/fc_train.hip.  The BN mode is the module's: training = batch
+    statistics (running statistics and num_batches_tracked updated as torch does), eval =
+    frozen running statistics.  Falls back to the modules for what the kernels do not cover:
+    more rows than pn2_fc_train_max_rows(), non-float32 or host tensors, a Linear without bias,
+    a non-affine BN, an eval-mode BN without running statistics; and for a train-mode BN on a
+    single row, where the modules raise their ValueError."""
+    ok = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and fc.bias is not None and
+          fc.weight.dtype == torch.float32 and 1 <= x.shape[0] <= ops.fc_train_max_rows())
+    if ok and bn is not None:
+        ok = bn.affine and bn.weight.dtype == torch.float32
+        if bn.training:
+            ok = ok and x.shape[0] > 1
+        else:
+            ok = ok and bn.running_mean is not None and bn.running_var is not None
+    if not ok:
+        y = fc(x) if bn is None else bn(fc(x))
+        return F.relu(y) if relu else y
+    if bn is None:
+        cfg = (0.0, 0.0, None, None, relu, False)
+        return _FcBnTrain.apply(x, cfg, fc.weight, fc.bias, None, None)
+    if bn.training:
+        mom = _bn_factor(bn)
+        cfg = (float(bn.eps), mom, bn.running_mean if mom > 0 else None,
+               bn.running_var if mom > 0 else None, relu, False)
+    else:
+        cfg = (float(bn.eps), 0.0, bn.running_mean, bn.running_var, relu, True)
+    return _FcBnTrain.apply(x, cfg, fc.weight, fc.bias, bn.weight, bn.bias)
+
+
 __all__ = ["mlp_max_train", "mlp_max_frozen", "point_mlp_train", "group_train", "eligible",
-           "eligible_frozen"]
+           "eligible_frozen", "linear_bn_train"]

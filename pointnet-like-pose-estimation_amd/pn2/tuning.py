@@ -41,6 +41,19 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      in a fixed order (include/pn2.h) -- with group_backward=1 an SA layer's
                      step then has no order-dependent sum.  Not tied to
                      torch.use_deterministic_algorithms.  0 or 1; anything else is an error
+    train_head       0: the heads' FC layers under autograd (the FC tails' fc1/bn1, fc2/bn2, fc3,
+                     the translation heads' mean MLP, the T-Nets' and the v1 heads' FC tails) are
+                     the torch modules: library GEMMs and BatchNorm1d's kernels, whose summation
+                     order is the library's choice; 1: pn2_fc_bn_forward_f32 /
+                     pn2_fc_bn_backward_f32 (+ pn2_gemm_nn_f32 for the input gradient) wherever
+                     the forward must be differentiable, in train mode (batch statistics) and
+                     in eval mode (frozen running statistics): one launch per layer and
+                     direction, every sum in a fixed order (include/pn2.h) -- with train_gemm=1
+                     and group_backward=1 a PointNet++ head's train step then has no
+                     order-dependent sum in any kernel of this project (dropout's mask, the
+                     loss and the optimizer stay torch).  Batches above
+                     pn2_fc_train_max_rows() rows keep the modules.  0 or 1; anything else is
+                     an error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -70,9 +83,10 @@ HOST_DEFAULTS = {
     "eval_grad": 1,
     "group_backward": 0,
     "train_gemm": 0,
+    "train_head": 0,
 }
 # host keys with a checked range (inclusive); the others take any integer
-HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1)}
+HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1)}
 
 
 def _check_host(key, value):

@@ -1,0 +1,195 @@
+"""The heads' FC layers under autograd: the torch modules (tuning train_head=0: library GEMMs,
+BatchNorm1d's kernels, ReLU and their backward) against pn2_fc_bn_forward_f32 /
+pn2_fc_bn_backward_f32 + pn2_gemm_nn_f32 (train_head=1, csrc/fc_train.hip), on identical inputs.
+
+  tail      the ClsSSG FC tail 1024 -> 512 -> 256 -> 7 (fc1/bn1/relu/drop, fc2/bn2/relu/drop, fc3)
+            forward + backward in train mode, at B = 24 and B = 32 rows
+  mean_mlp  the TranslationSSG mean MLP 3 -> 6 -> 3 (mean_fc1/mean_bn1/relu, mean_fc2), B = 24
+  step      the whole ClsSSG train step at B = 32 clouds of 1024 points (forward, nll_loss,
+            backward, SGD step) at train_head 0 / 1 with the other keys at their defaults, and
+            once with the three reproducibility keys on (train_gemm=1, group_backward=1,
+            train_head=1)
+  eval_grad the ClsSSG eval-mode forward under autograd (B = 32, N = 1024) at train_head 0 / 1,
+            and under no_grad for scale
+
+tail, mean_mlp, eval_grad: HIP events around `reps` back-to-back calls after `warmup` calls, the
+routes interleaved within each of `rounds` rounds; median (min, max) of the rounds.  step: wall
+clock over 20 synchronised steps after 3 (tools/bench_train.py's method), the routes interleaved
+over the rounds.  ratio = modules median / kernels median (> 1: the kernels are faster).
+Needs a ROCm device.  Writes one JSON document (default profiles/fc_train/timing.json) and
+prints it."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
+                os.path.join(ROOT, "tests", "golden")]
+import cases  # noqa: E402
+from pn2 import heads as H  # noqa: E402
+from pn2 import ops, tuning  # noqa: E402
+
+REPRO = {"train_gemm": 1, "group_backward": 1, "train_head": 1}
+
+
+def summary(ms):
+    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def interleaved(runs, a):
+    """runs: name -> (tuning keys, fn).  -> name -> summary of the rounds' ms per call."""
+    for keys, fn in runs.values():
+        with tuning.override(**keys):
+            for _ in range(a.warmup):
+                fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, (keys, fn) in runs.items():
+            with tuning.override(**keys):
+                ms[k].append(timed(fn, a.reps))
+    return ms
+
+
+def two_routes(fn, a):
+    ms = interleaved({"modules": ({"train_head": 0}, fn), "kernels": ({"train_head": 1}, fn)}, a)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"ms": {k: summary(v) for k, v in ms.items()},
+            "ratio_modules_over_kernels": round(med["modules"] / med["kernels"], 3)}
+
+
+def bench_tail(B, a):
+    torch.manual_seed(0)
+    model = H.ClsSSG().cuda().train()
+    x = torch.randn(B, 1024, generator=torch.Generator().manual_seed(1)).cuda().requires_grad_(True)
+    R = torch.randn(B, 7, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def fwd_bwd():
+        model.zero_grad(set_to_none=True)
+        x.grad = None
+        model._fc(x).backward(R)
+
+    def fwd():
+        with torch.no_grad():  # train mode: still the differentiable route, nothing recorded
+            model._fc(x)
+
+    out = {"B": B, "chain": [1024, 512, 256, 7], "forward_backward": two_routes(fwd_bwd, a),
+           "forward_only": two_routes(fwd, a)}
+    with tuning.override(train_head=1), ops.kernel_timer() as t:
+        fwd_bwd()
+    out["kernel_ms_one_step"] = {k: round(v["ms"], 4) for k, v in t.summary().items()}
+    return out
+
+
+def bench_mean_mlp(B, a):
+    torch.manual_seed(0)
+    model = H.TranslationSSG().cuda().train()
+    x = torch.randn(B, 3, generator=torch.Generator().manual_seed(3)).cuda().requires_grad_(True)
+    R = torch.randn(B, 3, generator=torch.Generator().manual_seed(4)).cuda()
+
+    def fwd_bwd():
+        model.zero_grad(set_to_none=True)
+        x.grad = None
+        model._mean_mlp(x).backward(R)
+
+    return {"B": B, "chain": [3, 6, 3], "forward_backward": two_routes(fwd_bwd, a)}
+
+
+def bench_step(B, a):
+    x = cases.cloud("uniform3", B, 1024, 5).permute(0, 2, 1).contiguous().cuda()
+    y = (torch.arange(B) % 7).cuda()
+    torch.manual_seed(0)
+    model = H.ClsSSG().cuda().train()
+    opt = torch.optim.SGD(model.parameters(), lr=1e-3, momentum=0.9)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        logp, _, _ = model(x)
+        F.nll_loss(logp, y).backward()
+        opt.step()
+
+    def run(keys):
+        with tuning.override(**keys):
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                step()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / 20 * 1e3
+
+    routes = {"train_head=0": {"train_head": 0}, "train_head=1": {"train_head": 1},
+              "train_gemm=1,group_backward=1,train_head=0": dict(REPRO, train_head=0),
+              "train_gemm=1,group_backward=1,train_head=1": REPRO}
+    ms = {k: [] for k in routes}
+    for _ in range(a.rounds):
+        for k, keys in routes.items():
+            ms[k].append(run(keys))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"model": "ClsSSG", "B": B, "N": 1024, "ms_per_step": {k: summary(v) for k, v in ms.items()},
+            "ratio_modules_over_kernels": round(med["train_head=0"] / med["train_head=1"], 3)}
+
+
+def bench_eval_grad(B, a):
+    x = cases.cloud("uniform3", B, 1024, 5).permute(0, 2, 1).contiguous().cuda()
+    model = cases.build_head(H.ClsSSG, 0).cuda().eval()
+
+    def fwd():
+        torch.manual_seed(0)
+        model(x)
+
+    def fwd_nograd():
+        with torch.no_grad():
+            fwd()
+
+    out = two_routes(fwd, a)
+    ms = interleaved({"no_grad": ({}, fwd_nograd)}, a)
+    out["ms"]["no_grad"] = summary(ms["no_grad"])
+    return dict(model="ClsSSG", B=B, N=1024, **out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fc_train", "timing.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_fc_train: needs a ROCm device")
+    doc = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "rounds": a.rounds, "warmup": a.warmup,
+           "max_rows": ops.fc_train_max_rows(),
+           "protocol": "HIP events around `reps` back-to-back calls per route (identical inputs), after "
+                       "`warmup` calls; routes interleaved within each of `rounds` rounds; median (min, "
+                       "max) of the rounds; ratio = modules median / kernels median.  step: wall clock "
+                       "over 20 synchronised train steps after 3, the routes interleaved",
+           "tail": {"B=%d" % B: bench_tail(B, a) for B in (24, 32)},
+           "mean_mlp": bench_mean_mlp(24, a),
+           "step": bench_step(32, a),
+           "eval_grad": bench_eval_grad(32, a)}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    text = json.dumps(doc, indent=1) + "\n"
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
