@@ -27,18 +27,23 @@
 //   pn2_bn_relu_group_max_f32 apply + group max in one pass over Y, A never written (the pooled
 //                             last layer of the frozen-statistics recompute, pn2/train.py)
 // Layout: channels-last rows [M][C] with row stride ld (the SA path's layout), so every pass is
-// a coalesced column-tiled sweep: a 256-thread block covers 64 columns x 4 row lanes of one row
-// chunk and reduces through LDS; chunk partials are merged in float64 by a per-column pass.
+// a coalesced column-tiled sweep: a 256-thread block covers 64 columns x its row lanes of one
+// row chunk; column sums reduce through LDS and chunk partials are merged in float64 by a
+// per-column pass.  The templated sweeps come in two widths: W = 1, a thread per column (64
+// column threads x 4 row lanes), and W = 4, a thread per 4 adjacent columns with one 16-byte
+// load or store per row (16 column threads x 16 row lanes) when C and the strides are multiples
+// of 4 and the bases 16-byte aligned (every SA / v1 layer; the host checks).  The 4-byte sweeps
+// reached 2.9 (partial) and 3.9 TB/s (apply) at SSG training sizes.
 #include "pn2_internal.h"
 
 namespace pn2 {
 
 constexpr int kTrCols = 64;     // columns per block
-constexpr int kTrLanes = 4;     // row lanes per block
+constexpr int kTrLanes = 4;     // row lanes per block of the one-column-per-thread sweeps
 constexpr int kTrChunk = 1024;  // rows per chunk (partials per chunk), at most
 constexpr int kTrChunkMin = 64;
 constexpr int kTrMinBlocks = 2048;  // column sweeps: enough blocks to fill 256 CUs several times
-constexpr int kTrUnroll = 8;    // rows in flight per thread in the column sweeps
+constexpr int kTrUnroll = 8;    // rows in flight per thread in the column sweeps (W = 4: 4)
 
 __device__ __forceinline__ float tr_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
 // xhat for the dgamma sum.  The float32 one is off by up to 2 ulp per row, which the sum over M
@@ -49,7 +54,47 @@ __device__ __forceinline__ double tr_xhat64(float y, float mean, float invstd) {
     return ((double)y - (double)mean) * (double)invstd;
 }
 
-// partial column sums of Y and Y^2 over row chunk blockIdx.y -> part[chunk][2][C] (double)
+// W adjacent elements of a row: one 16-byte load for W = 4, through vector type V4.  The max
+// kernels pass HIP's float4: with the compiler's own vector type the fused narrow one allocates
+// 68 registers instead of 59 and loses a wave per SIMD; the backward sweeps allocate the same
+// either way and measured 4-7% slower with float4.
+template <typename T>
+using tr_vec4 = T __attribute__((ext_vector_type(4)));
+
+template <int W, typename T, typename V4 = tr_vec4<T>>
+__device__ __forceinline__ void tr_load_row(const T *p, T (&v)[W]) {
+    if constexpr (W == 4) {
+        const V4 t = *reinterpret_cast<const V4 *>(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+// The block's two float64 column sums -> part[chunk blockIdx.y][p][C].  Row lane `lane` hands
+// in its sums s[p][j] of columns col + j of the block's tile; each (p, column) is finished by
+// one thread adding the LANES lane sums in ascending lane order.
+template <int LANES, int W>
+__device__ __forceinline__ void tr_col_reduce(const double (&s)[2][W], int lane, int col, int64_t C,
+                                              double *__restrict__ part) {
+    __shared__ double red[2][LANES][kTrCols];
+#pragma unroll
+    for (int j = 0; j < W; ++j) red[0][lane][col + j] = s[0][j], red[1][lane][col + j] = s[1][j];
+    __syncthreads();
+    if (threadIdx.x < 2 * kTrCols) {
+        const int p = threadIdx.x / kTrCols, cl = threadIdx.x % kTrCols;
+        const int64_t c = (int64_t)blockIdx.x * kTrCols + cl;
+        if (c < C) {
+            double t = red[p][0][cl];
+            for (int l = 1; l < LANES; ++l) t += red[p][l][cl];
+            part[((int64_t)blockIdx.y * 2 + p) * C + c] = t;
+        }
+    }
+}
+
+// partial column sums of Y and Y^2 over row chunk blockIdx.y -> part[chunk][2][C] (double).  The
+// reduction is tr_col_reduce<kTrLanes, 1> written out, the first lane adding to its own registers:
+// through the helper this kernel measured 6% slower on the 64-row chunks of the PointNet-v1 layers.
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float *__restrict__ Y, int64_t M,
                                                                int64_t C, int64_t ld, int64_t chunk,
                                                                double *__restrict__ part) {
@@ -124,7 +169,7 @@ __global__ __launch_bounds__(64) void bn_stats_final_kernel(const double *__rest
     }
 }
 
-// elementwise sweeps: block (64 columns x 4 row lanes) walks kTrEwRows rows of its column tile
+// elementwise sweeps: a block walks kTrEwRows rows of its column tile
 constexpr int kTrEwRows = 64;
 
 __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restrict__ Y, int64_t M,
@@ -148,152 +193,60 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restr
     }
 }
 
-// one thread per (group, column): max over the group's K rows, first index of the max
-__global__ __launch_bounds__(256) void group_max_kernel(const float *__restrict__ A, int64_t G,
-                                                        int64_t K, int64_t C, int64_t lda,
-                                                        float *__restrict__ out, int64_t ldo,
-                                                        int32_t *__restrict__ arg) {
-    const int tx = threadIdx.x & (kTrCols - 1), ty = threadIdx.x / kTrCols;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
-    const int64_t g = (int64_t)blockIdx.y * kTrLanes + ty;
-    if (c >= C || g >= G) return;
-    const float *p = A + g * K * lda + c;
-    float m = p[0];
-    int32_t a = 0;
-    int64_t k = 1;
-    for (; k + 8 <= K; k += 8) {  // 8 rows in flight
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(k + u) * lda];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (v[u] > m || (v[u] != v[u] && m == m)) m = v[u], a = (int32_t)(k + u);  // NaN wins
-    }
-    for (; k < K; ++k) {
-        const float v = p[k * lda];
-        if (v > m || (v != v && m == m)) m = v, a = (int32_t)k;  // NaN wins, as torch.max
-    }
-    out[g * ldo + c] = m;
-    arg[g * C + c] = a;
-}
-
-// (v, a) beats (m, b) in the max's order: NaN above every number, then value, then the first
-// index (torch.max's first argmax)
-__device__ __forceinline__ bool tr_better(float v, int32_t a, float m, int32_t b) {
-    if (v != v) return m == m || a < b;
-    if (m != m) return false;
-    return v > m || (v == m && a < b);
-}
-
-// One row of a lane's walk in increasing row order: strict > keeps the first maximum, a NaN
-// replaces a number only, the lane's first row replaces the start value.  Written as selects on
-// one flag: as a branch around the two assignments, the last row of the unrolled round came out
-// of the compiler updating m but not a when v was NaN (ROCm 7 clang, read in the ISA; caught by
-// tests/test_gpu_train_kernels.py test_group_max with a NaN on row 121 of K = 257).
-__device__ __forceinline__ void tr_take(float v, int32_t i, float &m, int32_t &a) {
-    const bool t = (v > m) | ((v != v) & (m == m)) | (a == 0x7fffffff);
-    m = t ? v : m;
-    a = t ? i : a;
-}
-
-// Large K (a PointNet-v1 max over a cloud's N points): one block per (group, 64 columns), the K
-// rows split over kTrWideLanes row lanes (8 rows in flight each), lanes merged through LDS.
-// One thread per (group, column) walking all K rows would serialise K/8 dependent load rounds.
-constexpr int kTrWideLanes = 16;
-constexpr int kTrWideK = 256;  // K from which the wide kernel is used
-
-__global__ __launch_bounds__(kTrCols * kTrWideLanes) void group_max_wide_kernel(
-    const float *__restrict__ A, int64_t K, int64_t C, int64_t lda, float *__restrict__ out, int64_t ldo,
-    int32_t *__restrict__ arg) {
-    __shared__ float sv[kTrWideLanes][kTrCols];
-    __shared__ int32_t sa[kTrWideLanes][kTrCols];
-    const int tx = threadIdx.x & (kTrCols - 1), ty = threadIdx.x / kTrCols;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
-    const int64_t g = blockIdx.y;
-    float m = -__builtin_inff();
-    int32_t a = 0x7fffffff;
-    if (c < C) {
-        const float *p = A + g * K * lda + c;
-        int64_t k = ty;
-        for (; k + 7 * kTrWideLanes < K; k += 8 * kTrWideLanes) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(k + u * kTrWideLanes) * lda];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) tr_take(v[u], (int32_t)(k + u * kTrWideLanes), m, a);
-        }
-        for (; k < K; k += kTrWideLanes) tr_take(p[k * lda], (int32_t)k, m, a);
-    }
-    sv[ty][tx] = m;
-    sa[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        for (int l = 1; l < kTrWideLanes; ++l)
-            if (sa[l][tx] != 0x7fffffff && tr_better(sv[l][tx], sa[l][tx], m, a)) m = sv[l][tx], a = sa[l][tx];
-        out[g * ldo + c] = m;
-        arg[g * C + c] = a;
-    }
-}
-
-// dXn of row r, column c (see header); dA dense [M][C] (ldd) or scattered from the max
-__device__ __forceinline__ float tr_dxn(const float *__restrict__ Y, int64_t ld, int64_t r, int64_t c,
-                                        float mean, float invstd, float gamma, float beta,
-                                        const float *__restrict__ dA, int64_t ldd,
-                                        const float *__restrict__ dOut, int64_t ldo,
-                                        const int32_t *__restrict__ arg, int64_t K, int64_t C,
-                                        int relu, float &y, float &xhat) {
-    // branch-free: every load is issued whatever the ReLU mask, so unrolled rows stay in flight
-    y = Y[r * ld + c];
-    xhat = tr_xhat(y, mean, invstd);
-    float d;
-    if (dA) {
-        d = dA[r * ldd + c];
-    } else {
-        // 32-bit division (the host checks M < 2^31): the 64-bit one is a long call sequence
-        const uint32_t g = (uint32_t)r / (uint32_t)K;
-        const float o = dOut[(int64_t)g * ldo + c];
-        d = arg[(int64_t)g * C + c] == (int32_t)((uint32_t)r - g * (uint32_t)K) ? o : 0.f;
-    }
+// dXn of one element (see header): the incoming gradient d behind the ReLU's mask
+__device__ __forceinline__ float tr_dxn(float xhat, float gamma, float beta, float d, int relu) {
     return !relu || xhat * gamma + beta > 0.f ? d : 0.f;
 }
 
+// one row's terms of S1 and S2
+template <int W>
+__device__ __forceinline__ void tr_bwd_sums(const float (&y)[W], const float (&d)[W], const float (&mu)[W],
+                                            const float (&is)[W], const float (&ga)[W], const float (&be)[W],
+                                            int relu, double (&s)[2][W]) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const float dd = tr_dxn(tr_xhat(y[j], mu[j], is[j]), ga[j], be[j], d[j], relu);
+        s[0][j] += (double)dd;
+        s[1][j] += (double)dd * tr_xhat64(y[j], mu[j], is[j]);
+    }
+}
+
+// partial column sums of dXn and dXn * xhat over row chunk blockIdx.y, dA dense (the non-max
+// layers) -> part[chunk][2][C]
+template <int W>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(
     const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
-    const float *__restrict__ dA, int64_t ldd, const float *__restrict__ dOut, int64_t ldo,
-    const int32_t *__restrict__ arg, int64_t K, int relu, int64_t chunk, double *__restrict__ part) {
-    __shared__ double red[2][kTrLanes][kTrCols];
-    const int tx = threadIdx.x & (kTrCols - 1), ty = threadIdx.x / kTrCols;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
+    const float *__restrict__ dA, int64_t ldd, int relu, int64_t chunk, double *__restrict__ part) {
+    constexpr int TX = kTrCols / W, TY = 256 / TX;
+    constexpr int U = W == 4 ? 4 : kTrUnroll;  // rows in flight (two loads each)
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx * W;
     const int64_t r0 = (int64_t)blockIdx.y * chunk;
     const int64_t r1 = r0 + chunk < M ? r0 + chunk : M;
-    double s1 = 0.0, s2 = 0.0;
-    if (c < C) {
-        const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+    double s[2][W] = {};
+    if (c < C) {  // W == 4: C % 4 == 0, so c < C covers c + 3
+        float mu[W], is[W], ga[W], be[W];
+        tr_load_row<W>(mean + c, mu), tr_load_row<W>(invstd + c, is);
+        tr_load_row<W>(gamma + c, ga), tr_load_row<W>(beta + c, be);
         int64_t r = r0 + ty;
-        for (; r + (kTrUnroll - 1) * kTrLanes < r1; r += kTrUnroll * kTrLanes) {
-            float d[kTrUnroll], y[kTrUnroll], xh;
+        for (; r + (U - 1) * TY < r1; r += U * TY) {
+            float y[U][W], d[U][W];
 #pragma unroll
-            for (int u = 0; u < kTrUnroll; ++u)
-                d[u] = tr_dxn(Y, ld, r + u * kTrLanes, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y[u], xh);
+            for (int u = 0; u < U; ++u) tr_load_row<W>(Y + (r + u * TY) * ld + c, y[u]);
 #pragma unroll
-            for (int u = 0; u < kTrUnroll; ++u) s1 += (double)d[u], s2 += (double)d[u] * tr_xhat64(y[u], mu, is);
+            for (int u = 0; u < U; ++u) tr_load_row<W>(dA + (r + u * TY) * ldd + c, d[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) tr_bwd_sums<W>(y[u], d[u], mu, is, ga, be, relu, s);
         }
-        for (; r < r1; r += kTrLanes) {
-            float y, xh;
-            const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y, xh);
-            s1 += (double)d;
-            s2 += (double)d * tr_xhat64(y, mu, is);
+        for (; r < r1; r += TY) {
+            float y[W], d[W];
+            tr_load_row<W>(Y + r * ld + c, y);
+            tr_load_row<W>(dA + r * ldd + c, d);
+            tr_bwd_sums<W>(y, d, mu, is, ga, be, relu, s);
         }
     }
-    red[0][ty][tx] = s1;
-    red[1][ty][tx] = s2;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        for (int l = 1; l < kTrLanes; ++l) s1 += red[0][l][tx], s2 += red[1][l][tx];
-        part[((int64_t)blockIdx.y * 2 + 0) * C + c] = s1;
-        part[((int64_t)blockIdx.y * 2 + 1) * C + c] = s2;
-    }
+    tr_col_reduce<TY, W>(s, ty, tx * W, C, part);
 }
 
 // The same column sums when dA is scattered from the max (the last layer): dXn is nonzero only
@@ -306,31 +259,20 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_gather_kernel(
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     const float *__restrict__ dOut, int64_t ldo, const int32_t *__restrict__ arg, int64_t K, int relu,
     int64_t chunk, double *__restrict__ part) {
-    __shared__ double red[2][kTrLanes][kTrCols];
     const int tx = threadIdx.x & (kTrCols - 1), ty = threadIdx.x / kTrCols;
     const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
     const int64_t g0 = (int64_t)blockIdx.y * chunk;
     const int64_t g1 = g0 + chunk < G ? g0 + chunk : G;
-    double s1 = 0.0, s2 = 0.0;
+    double s[2][1] = {};
     if (c < C) {
-        const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+        const float mu[1] = {mean[c]}, is[1] = {invstd[c]}, ga[1] = {gamma[c]}, be[1] = {beta[c]};
         for (int64_t g = g0 + ty; g < g1; g += kTrLanes) {
             const int64_t r = g * K + arg[g * C + c];
-            const float y = Y[r * ld + c];
-            const float xh = tr_xhat(y, mu, is);
-            const float d = !relu || xh * ga + be > 0.f ? dOut[g * ldo + c] : 0.f;
-            s1 += (double)d;
-            s2 += (double)d * tr_xhat64(y, mu, is);
+            const float y[1] = {Y[r * ld + c]}, d[1] = {dOut[g * ldo + c]};
+            tr_bwd_sums<1>(y, d, mu, is, ga, be, relu, s);
         }
     }
-    red[0][ty][tx] = s1;
-    red[1][ty][tx] = s2;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        for (int l = 1; l < kTrLanes; ++l) s1 += red[0][l][tx], s2 += red[1][l][tx];
-        part[((int64_t)blockIdx.y * 2 + 0) * C + c] = s1;
-        part[((int64_t)blockIdx.y * 2 + 1) * C + c] = s2;
-    }
+    tr_col_reduce<kTrLanes, 1>(s, ty, tx, C, part);
 }
 
 // FROZEN (PN2_LAYER_FROZEN_STATS): mean / invstd are constants of the caller (running statistics),
@@ -357,182 +299,123 @@ __global__ __launch_bounds__(64) void bn_bwd_final_kernel(const double *__restri
     }
 }
 
-template <bool FROZEN>
+// dY = gamma * invstd * (dXn - S1/M - xhat * S2/M) (FROZEN: dY = gamma * invstd * dXn), dA dense
+// [M][C] (ldd) or scattered from the max (dOut, arg, K).  Each thread holds 4 rows in flight per
+// round; their loads are clamped to the last row, so they stay branch-free.
+template <int W, bool FROZEN>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     const float *__restrict__ dA, int64_t ldd, const float *__restrict__ dOut, int64_t ldo,
     const int32_t *__restrict__ arg, int64_t K, int relu, const double *__restrict__ sums,
     float *__restrict__ dY, int64_t ldy) {
-    const int tx = threadIdx.x & (kTrCols - 1), ty = threadIdx.x / kTrCols;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx;
+    constexpr int TX = kTrCols / W, TY = 256 / TX, U = 4;
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const int64_t c = (int64_t)blockIdx.x * kTrCols + tx * W;
     if (c >= C) return;
-    const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    float m1 = 0.f, m2 = 0.f;
-    if constexpr (!FROZEN) m1 = (float)(sums[c] / (double)M), m2 = (float)(sums[C + c] / (double)M);
-    const int64_t r0 = (int64_t)blockIdx.y * kTrEwRows;
-    const int64_t r1 = r0 + kTrEwRows < M ? r0 + kTrEwRows : M;
-#pragma unroll 4
-    for (int64_t r = r0 + ty; r < r1; r += kTrLanes) {
-        float y, xh;
-        const float d = tr_dxn(Y, ld, r, c, mu, is, ga, be, dA, ldd, dOut, ldo, arg, K, C, relu, y, xh);
-        if constexpr (FROZEN)
-            dY[r * ldy + c] = ga * is * d;
-        else
-            dY[r * ldy + c] = ga * is * (d - m1 - xh * m2);
-    }
-}
-
-// ---- 16-byte variants (C, ld, ldd, ldy multiples of 4, 16-byte aligned bases: every SA / v1
-// layer): a thread covers 4 adjacent columns with one dwordx4 load or store per row, a block 64
-// columns x 16 row lanes.  The scalar sweeps issued 4-byte loads and reached 2.9 (partial) and
-// 3.9 TB/s (apply) at SSG training sizes.
-constexpr int kTrVecLanes = 16;
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
-// partial column sums of dXn and dXn * xhat, dA dense (the non-max layers)
-__global__ __launch_bounds__(256) void bn_bwd_partial_vec_kernel(
-    const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
-    const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
-    const float *__restrict__ dA, int64_t ldd, int relu, int64_t chunk, double *__restrict__ part) {
-    __shared__ double red[2][kTrVecLanes][kTrCols];
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + cq * 4;
-    const int64_t r0 = (int64_t)blockIdx.y * chunk;
-    const int64_t r1 = r0 + chunk < M ? r0 + chunk : M;
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    if (c < C) {
-        const float4 mu = ld4(mean + c), is = ld4(invstd + c), ga = ld4(gamma + c), be = ld4(beta + c);
-        const float mus[4] = {mu.x, mu.y, mu.z, mu.w}, iss[4] = {is.x, is.y, is.z, is.w};
-        const float gas[4] = {ga.x, ga.y, ga.z, ga.w}, bes[4] = {be.x, be.y, be.z, be.w};
-        int64_t r = r0 + rl;
-        constexpr int U = 4;  // rows in flight per thread (2 x 16-byte loads each)
-        for (; r + (U - 1) * kTrVecLanes < r1; r += U * kTrVecLanes) {
-            float4 y[U], d[U];
+    float mu[W], is[W], ga[W], be[W], m1[W], m2[W];
 #pragma unroll
-            for (int u = 0; u < U; ++u) y[u] = ld4(Y + (r + u * kTrVecLanes) * ld + c);
-#pragma unroll
-            for (int u = 0; u < U; ++u) d[u] = ld4(dA + (r + u * kTrVecLanes) * ldd + c);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float yv[4] = {y[u].x, y[u].y, y[u].z, y[u].w}, dv[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float xh = tr_xhat(yv[j], mus[j], iss[j]);
-                    const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
-                    s1[j] += (double)dd;
-                    s2[j] += (double)dd * tr_xhat64(yv[j], mus[j], iss[j]);
-                }
-            }
-        }
-        for (; r < r1; r += kTrVecLanes) {
-            const float4 y = ld4(Y + r * ld + c), d = ld4(dA + r * ldd + c);
-            const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = tr_xhat(yv[j], mus[j], iss[j]);
-                const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
-                s1[j] += (double)dd;
-                s2[j] += (double)dd * tr_xhat64(yv[j], mus[j], iss[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[0][rl][cq * 4 + j] = s1[j], red[1][rl][cq * 4 + j] = s2[j];
-    __syncthreads();
-    // 128 threads finish: (sum p, column) over the 16 row lanes
-    if (threadIdx.x < 2 * kTrCols) {
-        const int pp = threadIdx.x / kTrCols, col = threadIdx.x % kTrCols;
-        const int64_t cc = (int64_t)blockIdx.x * kTrCols + col;
-        if (cc < C) {
-            double t = 0.0;
-            for (int l = 0; l < kTrVecLanes; ++l) t += red[pp][l][col];
-            part[((int64_t)blockIdx.y * 2 + pp) * C + cc] = t;
-        }
-    }
-}
-
-// dY = gamma * invstd * (dXn - S1/M - xhat * S2/M), dA dense or scattered from the max
-// (FROZEN: dY = gamma * invstd * dXn)
-template <bool FROZEN>
-__global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(
-    const float *__restrict__ Y, int64_t M, int64_t C, int64_t ld, const float *__restrict__ mean,
-    const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
-    const float *__restrict__ dA, int64_t ldd, const float *__restrict__ dOut, int64_t ldo,
-    const int32_t *__restrict__ arg, int64_t K, int relu, const double *__restrict__ sums,
-    float *__restrict__ dY, int64_t ldy) {
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int64_t c = (int64_t)blockIdx.x * kTrCols + cq * 4;
-    if (c >= C) return;
-    float mus[4], iss[4], gas[4], bes[4], m1[4], m2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        mus[j] = mean[c + j], iss[j] = invstd[c + j], gas[j] = gamma[c + j], bes[j] = beta[c + j];
+    for (int j = 0; j < W; ++j) {
+        mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
         if constexpr (FROZEN)
             m1[j] = m2[j] = 0.f;
         else
             m1[j] = (float)(sums[c + j] / (double)M), m2[j] = (float)(sums[C + c + j] / (double)M);
     }
     const int64_t r0 = (int64_t)blockIdx.y * kTrEwRows;
-    constexpr int U = kTrEwRows / kTrVecLanes;  // 4 rows per thread, all in flight
-    float4 y[U], d[U];
+    constexpr int ROUNDS = kTrEwRows / (U * TY);  // W = 1: 4, W = 4: 1
+    for (int q = 0; q < ROUNDS; ++q) {
+        const int64_t rb = r0 + ty + q * (U * TY);
+        if (rb >= M) break;
+        float y[U][W], d[U][W];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t r = r0 + rl + u * kTrVecLanes;
-        const int64_t rr = r < M ? r : M - 1;  // clamped: loads stay branch-free
-        y[u] = ld4(Y + rr * ld + c);
-        if (dA) {
-            d[u] = ld4(dA + rr * ldd + c);
-        } else {
-            const uint32_t g = (uint32_t)rr / (uint32_t)K, k = (uint32_t)rr - g * (uint32_t)K;
-            const float4 o = ld4(dOut + (int64_t)g * ldo + c);
-            const int4 a = *reinterpret_cast<const int4 *>(arg + (int64_t)g * C + c);
-            d[u] = make_float4(a.x == (int32_t)k ? o.x : 0.f, a.y == (int32_t)k ? o.y : 0.f,
-                               a.z == (int32_t)k ? o.z : 0.f, a.w == (int32_t)k ? o.w : 0.f);
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = rb + u * TY;
+            const int64_t rr = r < M ? r : M - 1;
+            tr_load_row<W>(Y + rr * ld + c, y[u]);
+            if (dA) {
+                tr_load_row<W>(dA + rr * ldd + c, d[u]);
+            } else {
+                // 32-bit division (the host checks M < 2^31): the 64-bit one is a long call sequence
+                const uint32_t g = (uint32_t)rr / (uint32_t)K, k = (uint32_t)rr - g * (uint32_t)K;
+                int32_t a[W];
+                tr_load_row<W>(dOut + (int64_t)g * ldo + c, d[u]);
+                tr_load_row<W>(arg + (int64_t)g * C + c, a);
+#pragma unroll
+                for (int j = 0; j < W; ++j) d[u][j] = a[j] == (int32_t)k ? d[u][j] : 0.f;
+            }
         }
-    }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t r = r0 + rl + u * kTrVecLanes;
-        if (r >= M) break;
-        const float yv[4] = {y[u].x, y[u].y, y[u].z, y[u].w}, dv[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
-        float o[4];
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = rb + u * TY;
+            if (r >= M) break;
+            float o[W];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xh = tr_xhat(yv[j], mus[j], iss[j]);
-            const float dd = !relu || xh * gas[j] + bes[j] > 0.f ? dv[j] : 0.f;
-            if constexpr (FROZEN)
-                o[j] = gas[j] * iss[j] * dd;
+            for (int j = 0; j < W; ++j) {
+                const float xh = tr_xhat(y[u][j], mu[j], is[j]);
+                const float dd = tr_dxn(xh, ga[j], be[j], d[u][j], relu);
+                if constexpr (FROZEN)
+                    o[j] = ga[j] * is[j] * dd;
+                else
+                    o[j] = ga[j] * is[j] * (dd - m1[j] - xh * m2[j]);
+            }
+            if constexpr (W == 4)
+                *reinterpret_cast<float4 *>(dY + r * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
             else
-                o[j] = gas[j] * iss[j] * (dd - m1[j] - xh * m2[j]);
+                dY[r * ldy + c] = o[0];
         }
-        *reinterpret_cast<float4 *>(dY + r * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
-// ---- BatchNorm + ReLU + max over the K rows in one pass over Y (pn2_bn_relu_group_max_f32): the
-// pooled last layer of the frozen-statistics recompute, whose activation A is only needed for
-// its max and argmax.  Each element is bn_relu_apply_kernel's expression (this file is compiled
-// without contraction, so the roundings are the same) and enters the walks of group_max_kernel /
-// group_max_wide_kernel, so out and arg are those of apply followed by pn2_group_max_f32.  No
-// LDS in the narrow kernel, 2 x 4 KiB in the wide one; the kernels read M*C*4 bytes once and
-// write G*C*8: HBM-bound (the A round trip they replace is 2*M*C*4 bytes).
-// W = 1: a thread per column.  W = 4: a thread per 4 adjacent columns, one 16-byte load per row
-// (C, ld, ldo multiples of 4 and 16-byte aligned bases, checked by the host).
-template <int W>
-__device__ __forceinline__ void tr_load_row(const float *p, float (&v)[W]) {
-    if constexpr (W == 4) {
-        const float4 t = ld4(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
+// ---- max over each K rows and its first argmax, with (ACT: pn2_bn_relu_group_max_f32) or
+// without (pn2_group_max_f32) BatchNorm + ReLU applied to every element on the way in.  The
+// fused form is the pooled last layer of the frozen-statistics recompute, whose activation A is
+// only needed for its max and argmax: each element is bn_relu_apply_kernel's expression (this
+// file is compiled without contraction, so the roundings are the same) and enters the same walk,
+// so out and arg are those of apply followed by pn2_group_max_f32.  No LDS in the narrow kernel,
+// 2 x 4 KiB in the wide one; the kernels read M*C*4 bytes once and write G*C*8: HBM-bound (the A
+// round trip the fused form replaces is 2*M*C*4 bytes).
+
+// (v, a) beats (m, b) in the max's order: NaN above every number, then value, then the first
+// index (torch.max's first argmax)
+__device__ __forceinline__ bool tr_better(float v, int32_t a, float m, int32_t b) {
+    if (v != v) return m == m || a < b;
+    if (m != m) return false;
+    return v > m || (v == m && a < b);
 }
 
+// One row of a lane's walk in increasing row order: strict > keeps the first maximum, a NaN
+// replaces a number only, the lane's first row replaces the start value.  Written as selects on
+// one flag: as a branch around the two assignments, the last row of the unrolled round came out
+// of the compiler updating m but not a when v was NaN (ROCm 7 clang, read in the ISA; caught by
+// tests/test_gpu_train_kernels.py test_group_max with a NaN on row 121 of K = 257).
+__device__ __forceinline__ void tr_take(float v, int32_t i, float &m, int32_t &a) {
+    const bool t = (v > m) | ((v != v) & (m == m)) | (a == 0x7fffffff);
+    m = t ? v : m;
+    a = t ? i : a;
+}
+
+// the element that enters the max: ACT applies BatchNorm (+ ReLU), else the value as read
+template <bool ACT>
 __device__ __forceinline__ float tr_act(float y, float mu, float is, float ga, float be, int relu) {
+    if constexpr (!ACT) return y;
     const float x = tr_xhat(y, mu, is) * ga + be;
     return relu ? (x > 0.f ? x : 0.f) : x;
+}
+
+// the per-column BatchNorm constants of a thread's W columns (ACT only: the pointers are null
+// otherwise and the values unused)
+template <int W, bool ACT>
+__device__ __forceinline__ void tr_act_consts(const float *mean, const float *invstd, const float *gamma,
+                                              const float *beta, int64_t c, float (&mu)[W], float (&is)[W],
+                                              float (&ga)[W], float (&be)[W]) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        if constexpr (ACT)
+            mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
+        else
+            mu[j] = is[j] = ga[j] = be[j] = 0.f;
+    }
 }
 
 template <int W>
@@ -547,7 +430,7 @@ __device__ __forceinline__ void tr_store_max(float *out, int32_t *arg, const flo
 }
 
 // small K: one thread per (group, W columns); blockIdx.x walks the groups (G has no 65535 limit)
-template <int W>
+template <int W, bool ACT>
 __global__ __launch_bounds__(256) void bn_relu_group_max_kernel(
     const float *__restrict__ Y, int64_t G, int64_t K, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -560,35 +443,42 @@ __global__ __launch_bounds__(256) void bn_relu_group_max_kernel(
     if (c >= C || g >= G) return;  // W == 4: C % 4 == 0, so c < C covers c + 3
     float mu[W], is[W], ga[W], be[W], m[W];
     int32_t a[W];
+    tr_act_consts<W, ACT>(mean, invstd, gamma, beta, c, mu, is, ga, be);
 #pragma unroll
-    for (int j = 0; j < W; ++j) {
-        mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
-        m[j] = -__builtin_inff(), a[j] = 0x7fffffff;
-    }
+    for (int j = 0; j < W; ++j) m[j] = -__builtin_inff(), a[j] = 0x7fffffff;
     const float *p = Y + g * K * ld + c;
     int64_t k = 0;
     for (; k + U <= K; k += U) {
         float v[U][W];
 #pragma unroll
-        for (int u = 0; u < U; ++u) tr_load_row<W>(p + (k + u) * ld, v[u]);
+        for (int u = 0; u < U; ++u) tr_load_row<W, float, float4>(p + (k + u) * ld, v[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int j = 0; j < W; ++j)
-                tr_take(tr_act(v[u][j], mu[j], is[j], ga[j], be[j], relu), (int32_t)(k + u), m[j], a[j]);
+                tr_take(tr_act<ACT>(v[u][j], mu[j], is[j], ga[j], be[j], relu), (int32_t)(k + u), m[j], a[j]);
     }
     for (; k < K; ++k) {
         float v[W];
-        tr_load_row<W>(p + k * ld, v);
+        tr_load_row<W, float, float4>(p + k * ld, v);
 #pragma unroll
-        for (int j = 0; j < W; ++j) tr_take(tr_act(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
+        for (int j = 0; j < W; ++j)
+            tr_take(tr_act<ACT>(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
     }
     tr_store_max<W>(out + g * ldo + c, arg + g * C + c, m, a);
 }
 
-// large K (the group_all layer, K = N): one block per (group, 64 columns), the rows split over
-// kTrWideLanes row lanes merged through LDS, as group_max_wide_kernel
-template <int W>
+// Large K (the group_all layer, a PointNet-v1 max over a cloud's N points): one block per (group,
+// 64 columns), the K rows split over kTrWideLanes row lanes (U rows in flight each), lanes merged
+// through LDS.  One thread per (group, column) walking all K rows would serialise K/8 dependent
+// load rounds.  Each entry point keeps the block order it had before the two were merged: the
+// plain max (the PointNet-v1 max over K = 1024 rows of 1024 columns) has its column tiles on
+// grid.x, so that neighbouring blocks read the same rows -- with the groups there it measured
+// 3.6% slower -- and the fused form its groups on grid.x.
+constexpr int kTrWideLanes = 16;
+constexpr int kTrWideK = 256;  // K from which the wide kernel is used
+
+template <int W, bool ACT>
 __global__ __launch_bounds__(kTrCols / W * kTrWideLanes) void bn_relu_group_max_wide_kernel(
     const float *__restrict__ Y, int64_t K, int64_t C, int64_t ld, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -598,34 +488,35 @@ __global__ __launch_bounds__(kTrCols / W * kTrWideLanes) void bn_relu_group_max_
     constexpr int TX = kTrCols / W;
     constexpr int U = W == 4 ? 4 : 8;
     const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-    const int64_t c = (int64_t)blockIdx.y * kTrCols + tx * W;
-    const int64_t g = blockIdx.x;
+    const unsigned tile = ACT ? blockIdx.y : blockIdx.x;
+    const int64_t c = (int64_t)tile * kTrCols + tx * W;
+    const int64_t g = ACT ? blockIdx.x : blockIdx.y;  // the host uses this form for G < 65536 only
     float m[W];
     int32_t a[W];
 #pragma unroll
     for (int j = 0; j < W; ++j) m[j] = -__builtin_inff(), a[j] = 0x7fffffff;
     if (c < C) {
         float mu[W], is[W], ga[W], be[W];
-#pragma unroll
-        for (int j = 0; j < W; ++j) mu[j] = mean[c + j], is[j] = invstd[c + j], ga[j] = gamma[c + j], be[j] = beta[c + j];
+        tr_act_consts<W, ACT>(mean, invstd, gamma, beta, c, mu, is, ga, be);
         const float *p = Y + g * K * ld + c;
         int64_t k = ty;
         for (; k + (U - 1) * kTrWideLanes < K; k += U * kTrWideLanes) {
             float v[U][W];
 #pragma unroll
-            for (int u = 0; u < U; ++u) tr_load_row<W>(p + (k + u * kTrWideLanes) * ld, v[u]);
+            for (int u = 0; u < U; ++u) tr_load_row<W, float, float4>(p + (k + u * kTrWideLanes) * ld, v[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
                 for (int j = 0; j < W; ++j)
-                    tr_take(tr_act(v[u][j], mu[j], is[j], ga[j], be[j], relu), (int32_t)(k + u * kTrWideLanes),
-                            m[j], a[j]);
+                    tr_take(tr_act<ACT>(v[u][j], mu[j], is[j], ga[j], be[j], relu),
+                            (int32_t)(k + u * kTrWideLanes), m[j], a[j]);
         }
         for (; k < K; k += kTrWideLanes) {
             float v[W];
-            tr_load_row<W>(p + k * ld, v);
+            tr_load_row<W, float, float4>(p + k * ld, v);
 #pragma unroll
-            for (int j = 0; j < W; ++j) tr_take(tr_act(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
+            for (int j = 0; j < W; ++j)
+                tr_take(tr_act<ACT>(v[j], mu[j], is[j], ga[j], be[j], relu), (int32_t)k, m[j], a[j]);
         }
     }
 #pragma unroll
@@ -633,7 +524,7 @@ __global__ __launch_bounds__(kTrCols / W * kTrWideLanes) void bn_relu_group_max_
     __syncthreads();
     // the first 64 threads finish one column each: lane 0 holds row 0 (K >= 1), later lanes may be empty
     const int col = threadIdx.x;
-    const int64_t cc = (int64_t)blockIdx.y * kTrCols + col;
+    const int64_t cc = (int64_t)tile * kTrCols + col;
     if (col < kTrCols && cc < C) {
         float bm = sv[0][col];
         int32_t ba = sa[0][col];
@@ -654,6 +545,11 @@ inline int64_t chunk_rows(int64_t M, int64_t C) {
     return ch;
 }
 inline int64_t chunks(int64_t M, int64_t C) { const int64_t ch = chunk_rows(M, C); return (M + ch - 1) / ch; }
+inline unsigned col_tiles(int64_t C) { return (unsigned)((C + kTrCols - 1) / kTrCols); }
+
+// every pointer 16-byte aligned (null counts as aligned)
+template <typename... P>
+inline bool aligned16(P... p) { return ((... | (uintptr_t)p) & 15) == 0; }
 
 }  // namespace pn2
 
@@ -674,8 +570,8 @@ extern "C" int pn2_bn_train_stats_f32(const float *Y, int64_t M, int64_t C, int6
     PN2_REQUIRE(momentum <= 0.0 || (running_mean && running_var), "pn2_bn_train_stats_f32: running stats");
     hipStream_t st = as_stream(stream);
     double *part = static_cast<double *>(ws);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)chunks(M, C)),
-                       dim3(256), 0, st, Y, M, C, ld, chunk_rows(M, C), part);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(col_tiles(C), (unsigned)chunks(M, C)), dim3(256), 0, st, Y, M,
+                       C, ld, chunk_rows(M, C), part);
     PN2_LAUNCH_CHECK("bn_stats_partial_kernel");
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3((unsigned)C), dim3(64), 0, st, part, chunks(M, C), M, C,
                        eps, momentum, running_mean, running_var, mean, invstd, sxhat);
@@ -690,8 +586,7 @@ extern "C" int pn2_bn_relu_apply_f32(const float *Y, int64_t M, int64_t C, int64
     PN2_REQUIRE(M >= 0 && C >= 1 && ld >= C && lda >= C, "pn2_bn_relu_apply_f32: bad shape");
     PN2_REQUIRE((flags & ~PN2_LAYER_NO_RELU) == 0, "pn2_bn_relu_apply_f32: unknown flags");
     if (M == 0) return PN2_OK;
-    hipLaunchKernelGGL(bn_relu_apply_kernel,
-                       dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)((M + kTrEwRows - 1) / kTrEwRows)),
+    hipLaunchKernelGGL(bn_relu_apply_kernel, dim3(col_tiles(C), (unsigned)((M + kTrEwRows - 1) / kTrEwRows)),
                        dim3(256), 0, as_stream(stream), Y, M, C, ld, mean, invstd, gamma, beta, A, lda,
                        (flags & PN2_LAYER_NO_RELU) ? 0 : 1);
     PN2_LAUNCH_CHECK("bn_relu_apply_kernel");
@@ -710,42 +605,41 @@ extern "C" int pn2_bn_train_forward_f32(const float *Y, int64_t M, int64_t C, in
     return pn2_bn_relu_apply_f32(Y, M, C, ld, stats, stats + C, gamma, beta, A, lda, flags, stream);
 }
 
+// the max of both entry points (ACT: with the activation): wide from K = kTrWideK on while the
+// groups fit grid.y, narrow otherwise
+static bool max_is_wide(int64_t G, int64_t K) { return K >= kTrWideK && G < 65536; }
+
+template <int W, bool ACT>
+static int launch_group_max(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld, const float *mean,
+                            const float *invstd, const float *gamma, const float *beta, float *out, int64_t ldo,
+                            int32_t *arg, int relu, hipStream_t st) {
+    constexpr int TX = kTrCols / W, TY = 256 / TX;
+    if (max_is_wide(G, K)) {
+        const dim3 grid = ACT ? dim3((unsigned)G, col_tiles(C)) : dim3(col_tiles(C), (unsigned)G);
+        hipLaunchKernelGGL((bn_relu_group_max_wide_kernel<W, ACT>), grid,
+                           dim3(TX * kTrWideLanes), 0, st, Y, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
+        PN2_LAUNCH_CHECK("bn_relu_group_max_wide_kernel");
+        return PN2_OK;
+    }
+    hipLaunchKernelGGL((bn_relu_group_max_kernel<W, ACT>), dim3((unsigned)((G + TY - 1) / TY), col_tiles(C)),
+                       dim3(256), 0, st, Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
+    PN2_LAUNCH_CHECK("bn_relu_group_max_kernel");
+    return PN2_OK;
+}
+
 extern "C" int pn2_group_max_f32(const float *A, int64_t G, int64_t K, int64_t C, int64_t lda, float *out,
                                  int64_t ldo, int32_t *arg, void *stream) {
     PN2_REQUIRE(A && out && arg, "pn2_group_max_f32: null pointer");
     PN2_REQUIRE(G >= 0 && K >= 1 && K < ((int64_t)1 << 31) && C >= 1 && lda >= C && ldo >= C,
                 "pn2_group_max_f32: bad shape");
     if (G == 0) return PN2_OK;
-    if (K >= kTrWideK && G < 65536) {
-        hipLaunchKernelGGL(group_max_wide_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)G),
-                           dim3(kTrCols * kTrWideLanes), 0, as_stream(stream), A, K, C, lda, out, ldo, arg);
-        PN2_LAUNCH_CHECK("group_max_wide_kernel");
-        return PN2_OK;
-    }
-    hipLaunchKernelGGL(group_max_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)((G + kTrLanes - 1) / kTrLanes)),
-                       dim3(256), 0, as_stream(stream), A, G, K, C, lda, out, ldo, arg);
-    PN2_LAUNCH_CHECK("group_max_kernel");
-    return PN2_OK;
-}
-
-template <int W>
-static int launch_bn_relu_group_max(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld, const float *mean,
-                                    const float *invstd, const float *gamma, const float *beta, float *out,
-                                    int64_t ldo, int32_t *arg, int relu, hipStream_t st) {
-    constexpr int TX = kTrCols / W, TY = 256 / TX;
-    const unsigned tiles = (unsigned)((C + kTrCols - 1) / kTrCols);
-    // G < 65536 is not a grid limit here (groups are on grid.x): it keeps the choice of form the
-    // same as pn2_group_max_f32's for every shape, whose wide kernel has its groups on grid.y
-    if (K >= kTrWideK && G < 65536) {
-        hipLaunchKernelGGL(bn_relu_group_max_wide_kernel<W>, dim3((unsigned)G, tiles), dim3(TX * kTrWideLanes), 0, st,
-                           Y, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
-        PN2_LAUNCH_CHECK("bn_relu_group_max_wide_kernel");
-        return PN2_OK;
-    }
-    hipLaunchKernelGGL(bn_relu_group_max_kernel<W>, dim3((unsigned)((G + TY - 1) / TY), tiles), dim3(256), 0, st, Y,
-                       G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu);
-    PN2_LAUNCH_CHECK("bn_relu_group_max_kernel");
-    return PN2_OK;
+    // the wide form stays on one column per thread, as it was measured
+    const bool vec4 = !max_is_wide(G, K) && (C % 4) == 0 && (lda % 4) == 0 && (ldo % 4) == 0 &&
+                      aligned16(A, out, arg);
+    return vec4 ? launch_group_max<4, false>(A, G, K, C, lda, nullptr, nullptr, nullptr, nullptr, out, ldo, arg, 0,
+                                             as_stream(stream))
+                : launch_group_max<1, false>(A, G, K, C, lda, nullptr, nullptr, nullptr, nullptr, out, ldo, arg, 0,
+                                             as_stream(stream));
 }
 
 extern "C" int pn2_bn_relu_group_max_f32(const float *Y, int64_t G, int64_t K, int64_t C, int64_t ld,
@@ -758,12 +652,26 @@ extern "C" int pn2_bn_relu_group_max_f32(const float *Y, int64_t G, int64_t K, i
     PN2_REQUIRE((flags & ~PN2_LAYER_NO_RELU) == 0, "pn2_bn_relu_group_max_f32: unknown flags");
     if (G == 0) return PN2_OK;
     const int relu = (flags & PN2_LAYER_NO_RELU) ? 0 : 1;
-    const bool vec4 = (C % 4) == 0 && (ld % 4) == 0 && (ldo % 4) == 0 &&
-                      (((uintptr_t)Y | (uintptr_t)out | (uintptr_t)arg) & 15) == 0;
-    return vec4 ? launch_bn_relu_group_max<4>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
-                                              as_stream(stream))
-                : launch_bn_relu_group_max<1>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
-                                              as_stream(stream));
+    const bool vec4 = (C % 4) == 0 && (ld % 4) == 0 && (ldo % 4) == 0 && aligned16(Y, out, arg);
+    return vec4 ? launch_group_max<4, true>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
+                                            as_stream(stream))
+                : launch_group_max<1, true>(Y, G, K, C, ld, mean, invstd, gamma, beta, out, ldo, arg, relu,
+                                            as_stream(stream));
+}
+
+// the backward's kernels for a column width and a statistics mode
+struct BwdKernels {
+    decltype(&bn_bwd_partial_kernel<1>) partial;
+    decltype(&bn_bwd_final_kernel<false>) merge;
+    decltype(&bn_bwd_apply_kernel<1, false>) apply;
+};
+template <int W, bool FROZEN>
+static BwdKernels bwd_kernels() {
+    return {bn_bwd_partial_kernel<W>, bn_bwd_final_kernel<FROZEN>, bn_bwd_apply_kernel<W, FROZEN>};
+}
+static BwdKernels pick_bwd_kernels(bool vec4, bool frozen) {
+    if (vec4) return frozen ? bwd_kernels<4, true>() : bwd_kernels<4, false>();
+    return frozen ? bwd_kernels<1, true>() : bwd_kernels<1, false>();
 }
 
 extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, int64_t ld, const float *mean,
@@ -785,23 +693,15 @@ extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, in
     hipStream_t st = as_stream(stream);
     double *part = static_cast<double *>(ws);
     double *sums = part + chunks(M, C) * 2 * C;
+    const bool vec4 = (C % 4) == 0 && (ld % 4) == 0 && (ldy % 4) == 0 && ((dA ? ldd : ldo) % 4) == 0 &&
+                      (dA ? aligned16(dA) : aligned16(dOut, arg)) &&
+                      aligned16(Y, dY, mean, invstd, gamma, beta);
+    const BwdKernels kn = pick_bwd_kernels(vec4, frozen);
     int64_t nch;
-    const bool vec4 = (C % 4) == 0 && (ld % 4) == 0 && (ldy % 4) == 0 && (!dA || (ldd % 4) == 0) &&
-                      (dA || (ldo % 4) == 0) &&
-                      (((uintptr_t)Y | (uintptr_t)dY | (uintptr_t)(dA ? (const void *)dA : (const void *)dOut) |
-                        (uintptr_t)(dA ? nullptr : (const void *)arg) | (uintptr_t)mean | (uintptr_t)invstd |
-                        (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
-    if (dA && vec4) {
+    if (dA) {
         nch = chunks(M, C);
-        hipLaunchKernelGGL(bn_bwd_partial_vec_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)nch),
-                           dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma, beta, dA, ldd, relu,
-                           chunk_rows(M, C), part);
-        PN2_LAUNCH_CHECK("bn_bwd_partial_vec_kernel");
-    } else if (dA) {
-        nch = chunks(M, C);
-        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)nch),
-                           dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma, beta, dA, ldd, dOut, ldo, arg, K,
-                           relu, chunk_rows(M, C), part);
+        hipLaunchKernelGGL(kn.partial, dim3(col_tiles(C), (unsigned)nch), dim3(256), 0, st, Y, M, C, ld, mean, invstd,
+                           gamma, beta, dA, ldd, relu, chunk_rows(M, C), part);
         PN2_LAUNCH_CHECK("bn_bwd_partial_kernel");
     } else {  // scattered from the max: only the G argmax rows contribute
         // The workspace holds chunks(M, C) partials.  chunk_rows(G, C) halves from another start
@@ -811,35 +711,15 @@ extern "C" int pn2_bn_relu_backward_f32(const float *Y, int64_t M, int64_t C, in
         int64_t gch = chunk_rows(G, C);
         while ((G + gch - 1) / gch > cap) gch <<= 1;
         nch = (G + gch - 1) / gch;
-        hipLaunchKernelGGL(bn_bwd_partial_gather_kernel, dim3((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)nch),
-                           dim3(256), 0, st, Y, G, C, ld, mean, invstd, gamma, beta, dOut, ldo, arg, K, relu, gch,
-                           part);
+        hipLaunchKernelGGL(bn_bwd_partial_gather_kernel, dim3(col_tiles(C), (unsigned)nch), dim3(256), 0, st, Y, G, C,
+                           ld, mean, invstd, gamma, beta, dOut, ldo, arg, K, relu, gch, part);
         PN2_LAUNCH_CHECK("bn_bwd_partial_gather_kernel");
     }
-    if (frozen)
-        hipLaunchKernelGGL(bn_bwd_final_kernel<true>, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma,
-                           invstd, sxhat, dbeta, dgamma, dbias, sums);
-    else
-        hipLaunchKernelGGL(bn_bwd_final_kernel<false>, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma,
-                           invstd, sxhat, dbeta, dgamma, dbias, sums);
+    hipLaunchKernelGGL(kn.merge, dim3((unsigned)C), dim3(64), 0, st, part, nch, M, C, gamma, invstd, sxhat, dbeta,
+                       dgamma, dbias, sums);
     PN2_LAUNCH_CHECK("bn_bwd_final_kernel");
-    const dim3 egrid((unsigned)((C + kTrCols - 1) / kTrCols), (unsigned)((M + kTrEwRows - 1) / kTrEwRows));
-    if (vec4) {
-        if (frozen)
-            hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<true>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd,
-                               gamma, beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<false>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd,
-                               gamma, beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
-        PN2_LAUNCH_CHECK("bn_bwd_apply_vec_kernel");
-    } else {
-        if (frozen)
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma,
-                               beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, egrid, dim3(256), 0, st, Y, M, C, ld, mean, invstd, gamma,
-                               beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
-        PN2_LAUNCH_CHECK("bn_bwd_apply_kernel");
-    }
+    hipLaunchKernelGGL(kn.apply, dim3(col_tiles(C), (unsigned)((M + kTrEwRows - 1) / kTrEwRows)), dim3(256), 0, st, Y,
+                       M, C, ld, mean, invstd, gamma, beta, dA, ldd, dOut, ldo, arg, K, relu, sums, dY, ldy);
+    PN2_LAUNCH_CHECK("bn_bwd_apply_kernel");
     return PN2_OK;
 }

@@ -20,6 +20,9 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
                       input gradient, weight gradient), every sum in a fixed order
   pn2::pack_layer     Conv2d 1x1 + BatchNorm2d (eval) parameters :150-156, :184-193
   pn2::sa_mlp_max_    gathered shared MLP + max :167-172, :211-218 (writes into `out`)
+  bn_train_forward_direct / bn_relu_apply_direct / group_max_direct / bn_relu_backward_direct
+                      (no dispatcher op) train-mode BatchNorm2d + ReLU + torch.max :169-172 and
+                      their backward on channels-last rows, around the GEMMs above
   pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
                       channels-last rows (the recompute of pn2.train's frozen mode)
 """
@@ -126,6 +129,22 @@ def _dev(t: Tensor, what: str):
 def _stream(t: Tensor) -> int:
     # this thread's device error slot first (a dict lookup once bound): kernels raise into it
     return _lib.stream_ptr(t.device)
+
+
+_WS = {}
+
+
+def _workspace(nbytes: int, device, stream: int) -> Tensor:
+    """Scratch of the kernels that merge partial sums (the BN sweeps' float64 column partials,
+    pn2_gemm_tn_f32's slab partials): one grow-only buffer per (device, stream).  Every use is
+    ordered on that stream and consumed inside the call that fills it, so all of them share it
+    (one allocation per step instead of one per call)."""
+    key = (device, stream)
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+        _WS[key] = ws
+    return ws
 
 
 def packed_stride(C: int) -> int:
@@ -401,20 +420,6 @@ def _matrix(t: Tensor, what: str) -> Tuple[Tensor, int]:
     return t, max(t.stride(0), 1)
 
 
-_GEMM_WS = {}
-
-
-def _gemm_workspace(nbytes: int, device, stream: int) -> Tensor:
-    """pn2_gemm_tn_f32's slab partials: one grow-only buffer per (device, stream) -- every use
-    is ordered on that stream."""
-    key = (device, stream)
-    ws = _GEMM_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _GEMM_WS[key] = ws
-    return ws
-
-
 def gemm_nt_direct(A: Tensor, B: Tensor, bias: Optional[Tensor]) -> Tensor:
     """A [M,K], B [N,K], bias [N] or None -> A B^T + bias [M,N] (pn2_gemm_nt_f32: each row of
     the result a function of that row of A, of B and of the bias only; ascending 16-wide steps
@@ -486,7 +491,7 @@ def gemm_tn_direct(A: Tensor, B: Tensor) -> Tensor:
     if nbytes < 0:
         raise ValueError("pn2::gemm_tn: bad shape M=%d N=%d K=%d" % (M, N, K))
     st = _stream(A)
-    ws = _gemm_workspace(nbytes, A.device, st)
+    ws = _workspace(nbytes, A.device, st)
     C = torch.empty(N, K, dtype=torch.float32, device=A.device)
     _run("pn2_gemm_tn_f32", _L.pn2_gemm_tn_f32,
          (A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), K, M, N, K, ws.data_ptr(), ws.numel(), st),
@@ -860,6 +865,108 @@ def fc_tail(x: Tensor, layers, logsoftmax: bool):
           p(amax), ws.data_ptr(), nbytes, _stream(x)), x.device,
          flops=2.0 * B * (K * N1 + N1 * N2 + N2 * N3))
     return out, amax
+
+
+# ------------------------------------------------------------------------------ training BN / ReLU / max
+# The sweeps of csrc/train.hip around the shared MLP's GEMMs (pn2.train's autograd function is
+# their only caller; no torch.library op: nothing needs the dispatcher).  Rows are read in
+# place through their row stride; outputs are allocated here, contiguous.
+def _bn_vectors(what: str, Y: Tensor, *vs) -> Tuple[int, ...]:
+    C = Y.shape[1]
+    return tuple(_vector(v, C, what, Y) for v in vs)
+
+
+def bn_train_forward_direct(Y: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optional[Tensor],
+                            running_var: Optional[Tensor], eps: float, momentum: float,
+                            relu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """Y [M, C] -> (A = act((Y - mean) * invstd * gamma + beta), stats [mean | invstd] 2C float32,
+    sxhat [C] float64) with the batch statistics of Y's columns (pn2_bn_train_forward_f32:
+    statistics sweep, then apply).  momentum > 0 with running statistics updates them in place
+    (torch's train-mode rule); otherwise they are not touched."""
+    what = "pn2::bn_train_forward"
+    Y, ld = _matrix(Y, what)
+    M, C = Y.shape
+    upd = momentum > 0.0 and running_mean is not None
+    A = torch.empty(M, C, dtype=torch.float32, device=Y.device)
+    stats = torch.empty(2 * C, dtype=torch.float32, device=Y.device)
+    sxhat = torch.empty(C, dtype=torch.float64, device=Y.device)
+    st = _stream(Y)
+    ws = _workspace(int(_L.pn2_bn_train_workspace_bytes(M, C)), Y.device, st)
+    _run("pn2_bn_train_forward_f32", _L.pn2_bn_train_forward_f32,
+         (Y.data_ptr(), M, C, ld, float(eps), float(momentum) if upd else 0.0,
+          *_bn_vectors(what, Y, running_mean if upd else None, running_var if upd else None, gamma, beta),
+          A.data_ptr(), C, 0 if relu else _lib.LAYER_NO_RELU, stats.data_ptr(), sxhat.data_ptr(),
+          ws.data_ptr(), ws.numel(), st), Y.device, nbytes=12.0 * M * C, flops=8.0 * M * C)
+    return A, stats, sxhat
+
+
+def bn_relu_apply_direct(Y: Tensor, mean: Tensor, invstd: Tensor, gamma: Tensor, beta: Tensor,
+                         relu: bool) -> Tensor:
+    """Y [M, C] -> A = act((Y - mean) * invstd * gamma + beta) with the caller's statistics
+    (pn2_bn_relu_apply_f32): a hidden layer of pn2.train's frozen mode."""
+    what = "pn2::bn_relu_apply"
+    Y, ld = _matrix(Y, what)
+    M, C = Y.shape
+    A = torch.empty(M, C, dtype=torch.float32, device=Y.device)
+    _run("pn2_bn_relu_apply_f32", _L.pn2_bn_relu_apply_f32,
+         (Y.data_ptr(), M, C, ld, *_bn_vectors(what, Y, mean, invstd, gamma, beta), A.data_ptr(), C,
+          0 if relu else _lib.LAYER_NO_RELU, _stream(Y)), Y.device, nbytes=8.0 * M * C, flops=5.0 * M * C)
+    return A
+
+
+def group_max_direct(A: Tensor, K: int) -> Tuple[Tensor, Tensor]:
+    """A [G*K, C] -> (max [G, C], first argmax [G, C] int32) over each K rows, a NaN above every
+    number as torch.max (pn2_group_max_f32)."""
+    A, lda = _matrix(A, "pn2::group_max")
+    M, C = A.shape
+    if K < 1 or M % K:
+        raise ValueError("pn2::group_max: A [G*K, C]")
+    G = M // K
+    out = torch.empty(G, C, dtype=torch.float32, device=A.device)
+    arg = torch.empty(G, C, dtype=torch.int32, device=A.device)
+    _run("pn2_group_max_f32", _L.pn2_group_max_f32,
+         (A.data_ptr(), G, K, C, lda, out.data_ptr(), C, arg.data_ptr(), _stream(A)), A.device,
+         nbytes=4.0 * M * C + 8.0 * G * C)
+    return out, arg
+
+
+def bn_relu_backward_direct(Y: Tensor, mean: Tensor, invstd: Tensor, gamma: Tensor, beta: Tensor,
+                            dA: Optional[Tensor], dOut: Optional[Tensor], arg: Optional[Tensor], K: int,
+                            sxhat: Optional[Tensor], relu: bool,
+                            frozen: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The backward of BatchNorm + ReLU on Y [M, C] (pn2_bn_relu_backward_f32) -> (dY [M, C],
+    dgamma, dbeta, dbias = sum of dY's rows).  The incoming gradient is dA [M, C], or, with dA
+    None, scattered from the max over each K rows: dOut [M/K, C] on the rows arg [M/K, C] int32
+    names.  sxhat is the forward's (None when frozen: the running statistics are constants)."""
+    what = "pn2::bn_relu_backward"
+    Y, ld = _matrix(Y, what)
+    M, C = Y.shape
+    if dA is not None:
+        d, ldd = _matrix(dA, what)
+        rows, ap = M, 0
+    else:
+        if dOut is None or arg is None:
+            raise ValueError("%s: dA, or dOut and arg of the max" % what)
+        d, ldd = _matrix(dOut, what)
+        rows = M // K if K >= 1 and M % K == 0 else -1
+        if arg.dtype != torch.int32 or tuple(arg.shape) != (rows, C) or not arg.is_contiguous():
+            raise ValueError("%s: arg [M/K, C] contiguous int32" % what)
+        ap = arg.data_ptr()
+    if tuple(d.shape) != (rows, C) or d.device != Y.device or (sxhat is None and not frozen):
+        raise ValueError("%s: dA [M, C] or dOut [M/K, C] on Y's device, sxhat unless frozen" % what)
+    dY = torch.empty(M, C, dtype=torch.float32, device=Y.device)
+    dgamma, dbeta, dbias = (torch.empty(C, dtype=torch.float32, device=Y.device) for _ in range(3))
+    st = _stream(Y)
+    ws = _workspace(int(_L.pn2_bn_train_workspace_bytes(M, C)), Y.device, st)
+    flags = (0 if relu else _lib.LAYER_NO_RELU) | (_lib.LAYER_FROZEN_STATS if frozen else 0)
+    dense = dA is not None
+    _run("pn2_bn_relu_backward_f32", _L.pn2_bn_relu_backward_f32,
+         (Y.data_ptr(), M, C, ld, *_bn_vectors(what, Y, mean, invstd, gamma, beta),
+          d.data_ptr() if dense else 0, ldd, 0 if dense else d.data_ptr(), ldd, ap, K,
+          0 if sxhat is None else sxhat.data_ptr(), dY.data_ptr(), C, dgamma.data_ptr(), dbeta.data_ptr(),
+          dbias.data_ptr(), ws.data_ptr(), ws.numel(), flags, st), Y.device,
+         nbytes=20.0 * M * C if dense else 8.0 * M * C + 20.0 * rows * C, flops=16.0 * M * C)
+    return dY, dgamma, dbeta, dbias
 
 
 # ------------------------------------------------------------------------------ bn_relu_group_max

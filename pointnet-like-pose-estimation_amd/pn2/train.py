@@ -12,8 +12,11 @@ kernels of csrc/train_gemm.hip (pn2_gemm_nt_f32 / pn2_gemm_nn_f32 / pn2_gemm_tn_
 products at fp32 accuracy, every sum in a fixed order -- include/pn2.h), so that a layer's step
 runs no library arithmetic.  The batch-statistics BatchNorm, ReLU, running-stat update,
 max + argmax and their backward are the fused HIP kernels of csrc/train.hip (one pass over the
-activations each).  BatchNorm semantics follow torch's train mode: biased variance normalises,
-running_var takes the unbiased one, momentum None = cumulative average, num_batches_tracked += 1.
+activations each), called like every other kernel through pn2.ops (bn_train_forward_direct,
+bn_relu_apply_direct, group_max_direct, bn_relu_backward_direct: ops.kernel_timer records them,
+and their float64 partials live in ops' per-stream workspace).  BatchNorm semantics follow
+torch's train mode: biased variance normalises, running_var takes the unbiased one, momentum
+None = cumulative average, num_batches_tracked += 1.
 
 The PointNet-v1 shared MLPs (Conv1d 1x1 -> train-mode BatchNorm1d -> ReLU, /root/reference/
 model/pointnet_utils.py:31-35, 118-128, and the v1 heads' conv stacks, rotation.py:37-43) are the
@@ -41,10 +44,8 @@ plus pn2_gemm_nn_f32 for the input gradient.
 import torch
 import torch.nn.functional as F
 
-from . import _lib
 from . import ops
 from . import tuning
-from .ops import _stream
 
 
 def eligible(grouped, convs, bns):
@@ -88,6 +89,18 @@ def _bn_factor(bn):
     return float(bn.momentum)
 
 
+def _bn_config(bn, relu, frozen):
+    """One layer's BatchNorm configuration for the autograd functions: (eps, momentum factor,
+    running_mean, running_var, relu, frozen).  Train mode (frozen False) takes torch's momentum
+    factor, counting the batch (_bn_factor), and names the running statistics only when they
+    are to be updated; frozen mode reads them and updates nothing."""
+    if frozen:
+        return (float(bn.eps), 0.0, bn.running_mean, bn.running_var, relu, True)
+    mom = _bn_factor(bn)
+    return (float(bn.eps), mom, bn.running_mean if mom > 0 else None,
+            bn.running_var if mom > 0 else None, relu, False)
+
+
 _CHUNK = 2048
 
 
@@ -107,95 +120,50 @@ def _grad_weight(dY, X):
     return g
 
 
-_WS = {}
-
-
-def _workspace(L, M, C, device, stream):
-    """The BN sweeps' float64 partials, one grow-only buffer per (device, stream): every use is
-    ordered on that stream, so forward and backward layers can share it (one allocation per
-    step instead of one per call)."""
-    need = int(L.pn2_bn_train_workspace_bytes(M, C))
-    key = (device, stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
-
-
 class _MlpMaxTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, K, cfg, *params):
-        """x0 [M, Cin] rows; cfg[l] = (eps, momentum factor, running_mean, running_var, flags);
-        params = (W, b, gamma, beta) per layer.  -> [M / K, Cout] max over each K rows, or the
-        last layer's [M, Cout] rows when K == 0.  A layer whose flags carry LAYER_FROZEN_STATS
+        """x0 [M, Cin] rows; cfg[l] = _bn_config's (eps, momentum factor, running_mean,
+        running_var, relu, frozen); params = (W, b, gamma, beta) per layer.  -> [M / K, Cout] max
+        over each K rows, or the last layer's [M, Cout] rows when K == 0.  A frozen layer
         normalises with (running_mean, rsqrt(running_var + eps)) and updates nothing."""
-        L = _lib.load()
         n = len(cfg)
-        M = x0.shape[0]
-        st = _stream(x0)
         fixed = ctx.fixed = tuning.get("train_gemm") == 1  # the backward takes the forward's route
         xs, ys, stats = [x0], [], []
         x, pooled = x0, None
         for l in range(n):
             W, b, g, be = params[4 * l:4 * l + 4]
-            eps, mom, rm, rv, flags = cfg[l]
+            eps, mom, rm, rv, relu, frozen = cfg[l]
             cout = W.shape[0]
             if fixed:
                 Y = ops.gemm_nt_direct(x, W.reshape(cout, -1), b)
             else:
                 Y = torch.addmm(b, x, W.reshape(cout, -1).t())
-            if flags & _lib.LAYER_FROZEN_STATS:
+            ys.append(Y)
+            if frozen:
                 mean, invstd = rm, torch.rsqrt(rv + eps)
-                ys.append(Y)
                 stats += [mean, invstd, None]  # no sxhat: the backward's sums need none
                 if l == n - 1 and K:  # max and argmax straight from Y: A is never written
-                    pooled, arg = ops.bn_relu_group_max_direct(Y, K, mean, invstd, g, be,
-                                                               not flags & _lib.LAYER_NO_RELU)
+                    pooled, arg = ops.bn_relu_group_max_direct(Y, K, mean, invstd, g, be, relu)
                     continue
-                ptrs = (mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), be.data_ptr())
-                x = torch.empty_like(Y)
-                _lib.check(L.pn2_bn_relu_apply_f32(
-                    Y.data_ptr(), M, cout, cout, *ptrs, x.data_ptr(), cout,
-                    flags & _lib.LAYER_NO_RELU, st), "pn2_bn_relu_apply_f32")
-                if l + 1 < n:
-                    xs.append(x)
-                continue
-            ws = _workspace(L, M, cout, x0.device, st)
-            st_mi = torch.empty(2 * cout, device=x0.device)  # [mean | invstd]
-            sxhat = torch.empty(cout, dtype=torch.float64, device=x0.device)
-            upd = mom > 0.0 and rm is not None
-            A = torch.empty_like(Y)
-            _lib.check(L.pn2_bn_train_forward_f32(
-                Y.data_ptr(), M, cout, cout, float(eps), float(mom) if upd else 0.0,
-                rm.data_ptr() if upd else 0, rv.data_ptr() if upd else 0, g.data_ptr(),
-                be.data_ptr(), A.data_ptr(), cout, flags, st_mi.data_ptr(), sxhat.data_ptr(),
-                ws.data_ptr(), ws.numel(), st), "pn2_bn_train_forward_f32")
-            ys.append(Y)
-            stats += [st_mi[:cout], st_mi[cout:], sxhat]
-            x = A
+                x = ops.bn_relu_apply_direct(Y, mean, invstd, g, be, relu)
+            else:
+                x, st_mi, sxhat = ops.bn_train_forward_direct(Y, g, be, rm, rv, eps, mom, relu)
+                stats += [st_mi[:cout], st_mi[cout:], sxhat]
             if l + 1 < n:
-                xs.append(A)
+                xs.append(x)
         ctx.K, ctx.n = K, n
-        ctx.flags = tuple(c[4] for c in cfg)
+        ctx.modes = tuple(c[4:] for c in cfg)  # (relu, frozen) per layer
         if not K:
             ctx.save_for_backward(*xs, *ys, *stats, *params)
             return x
-        if pooled is not None:
-            ctx.save_for_backward(*xs, *ys, *stats, arg, *params)
-            return pooled
-        G = M // K
-        cout = x.shape[1]
-        out = torch.empty(G, cout, device=x0.device)
-        arg = torch.empty(G, cout, dtype=torch.int32, device=x0.device)
-        _lib.check(L.pn2_group_max_f32(x.data_ptr(), G, K, cout, cout, out.data_ptr(), cout,
-                                       arg.data_ptr(), st), "pn2_group_max_f32")
+        if pooled is None:
+            pooled, arg = ops.group_max_direct(x, K)
         ctx.save_for_backward(*xs, *ys, *stats, arg, *params)
-        return out
+        return pooled
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.load()
         n, K = ctx.n, ctx.K
         saved = ctx.saved_tensors
         xs = saved[:n]
@@ -204,30 +172,18 @@ class _MlpMaxTrain(torch.autograd.Function):
         arg = saved[5 * n] if K else None
         params = saved[5 * n + (1 if K else 0):]
         dout = dout.contiguous()
-        M = xs[0].shape[0]
-        st = _stream(dout)
         grads = [None] * (4 * n)
         dA = None if K else dout  # K == 0: the rows' gradient is dense
         for l in reversed(range(n)):
             W, b, g, be = params[4 * l:4 * l + 4]
-            Y = ys[l]
-            mean, invstd, sxhat = stats[3 * l], stats[3 * l + 1], stats[3 * l + 2]
-            cout = Y.shape[1]
-            ws = _workspace(L, M, cout, Y.device, st)
-            dY = torch.empty_like(Y)
-            dgamma = torch.empty(cout, device=Y.device)
-            dbeta = torch.empty(cout, device=Y.device)
-            dbias = torch.empty(cout, device=Y.device)
-            last = l == n - 1 and K
-            _lib.check(L.pn2_bn_relu_backward_f32(
-                Y.data_ptr(), M, cout, cout, mean.data_ptr(), invstd.data_ptr(), g.data_ptr(),
-                be.data_ptr(), 0 if last else dA.data_ptr(), cout,
-                dout.data_ptr() if last else 0, cout, arg.data_ptr() if last else 0, K,
-                0 if sxhat is None else sxhat.data_ptr(), dY.data_ptr(), cout, dgamma.data_ptr(), dbeta.data_ptr(),
-                dbias.data_ptr(), ws.data_ptr(), ws.numel(), ctx.flags[l], st),
-                "pn2_bn_relu_backward_f32")
+            mean, invstd, sxhat = stats[3 * l:3 * l + 3]
+            relu, frozen = ctx.modes[l]
+            last = l == n - 1 and K  # the max's layer: dout scattered to the argmax rows
+            dY, dgamma, dbeta, dbias = ops.bn_relu_backward_direct(
+                ys[l], mean, invstd, g, be, None if last else dA, dout if last else None,
+                arg if last else None, K, sxhat, relu, frozen)
             X = xs[l]
-            W2 = W.reshape(cout, -1)
+            W2 = W.reshape(W.shape[0], -1)
             grads[4 * l] = (ops.gemm_tn_direct(dY, X) if ctx.fixed else _grad_weight(dY, X)).view_as(W)
             grads[4 * l + 1] = dbias  # sum_r dY, from the BN sums (no extra pass over dY)
             grads[4 * l + 2] = dgamma
@@ -286,10 +242,7 @@ def _apply(x0, K, convs, bns, last_relu=True):
     cfg, params = [], []
     n = len(convs)
     for l, (conv, bn) in enumerate(zip(convs, bns)):
-        mom = _bn_factor(bn)
-        flags = _lib.LAYER_NO_RELU if (l == n - 1 and not last_relu) else 0
-        cfg.append((bn.eps, mom, bn.running_mean if mom > 0 else None,
-                    bn.running_var if mom > 0 else None, flags))
+        cfg.append(_bn_config(bn, last_relu or l < n - 1, False))
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
     return _MlpMaxTrain.apply(x0, K, tuple(cfg), *params)
 
@@ -305,7 +258,7 @@ def mlp_max_frozen(grouped, convs, bns):
         x0 = x0.contiguous()
     cfg, params = [], []
     for conv, bn in zip(convs, bns):
-        cfg.append((float(bn.eps), 0.0, bn.running_mean, bn.running_var, _lib.LAYER_FROZEN_STATS))
+        cfg.append(_bn_config(bn, True, True))
         params += [conv.weight, conv.bias, bn.weight, bn.bias]
     out = _MlpMaxTrain.apply(x0, K, tuple(cfg), *params)
     return out.view(B, S, -1).permute(0, 2, 1)
@@ -393,13 +346,7 @@ def linear_bn_train(x, fc, bn, relu=True):
     if bn is None:
         cfg = (0.0, 0.0, None, None, relu, False)
         return _FcBnTrain.apply(x, cfg, fc.weight, fc.bias, None, None)
-    if bn.training:
-        mom = _bn_factor(bn)
-        cfg = (float(bn.eps), mom, bn.running_mean if mom > 0 else None,
-               bn.running_var if mom > 0 else None, relu, False)
-    else:
-        cfg = (float(bn.eps), 0.0, bn.running_mean, bn.running_var, relu, True)
-    return _FcBnTrain.apply(x, cfg, fc.weight, fc.bias, bn.weight, bn.bias)
+    return _FcBnTrain.apply(x, _bn_config(bn, relu, not bn.training), fc.weight, fc.bias, bn.weight, bn.bias)
 
 
 __all__ = ["mlp_max_train", "mlp_max_frozen", "point_mlp_train", "group_train", "eligible",

@@ -364,3 +364,31 @@ def test_group_max(K, C):
 def test_group_max_many_wide_groups():
     """G = 65536 groups of K = 256: past the wide kernel's grid, back on the narrow kernel."""
     check_group_max(65536, 256, 2, 0, 0)
+
+
+@pytest.mark.parametrize("K,C", [(2, 1), (1, 5)])
+def test_group_max_many_groups(K, C):
+    """G = 262145 groups of a small K: one more block of groups than a grid's second dimension
+    holds (4 groups per block x 65535), where the launch used to be refused.  Small integers
+    (ties) throughout; group 0 and the last group hold a NaN, and where K allows it a tie:
+    K = 2 gives them two NaNs (the first wins), and their neighbours a NaN after a number and
+    two equal numbers."""
+    lib, L = _lib()
+    G = 262145
+    rng = np.random.default_rng(7 * K + C)
+    a = rng.integers(-3, 4, (G, K, C)).astype(np.float32)
+    a[0, :, 0] = np.nan
+    a[G - 1, :, C - 1] = np.nan
+    if K > 1:
+        a[1, :, 0] = [1.0, np.nan]
+        a[G - 2, :, C - 1] = [3.0, 3.0]
+    a = a.reshape(G * K, C)
+    keep, Ap, lda = rows_in(a, 0)
+    out, op, ldo = rows_out(G, C, 0)
+    arg = torch.full((G, C), -1, dtype=torch.int32, device="cuda")
+    lib.check(L.pn2_group_max_f32(Ap, G, K, C, lda, op, ldo, arg.data_ptr(), _st(keep)), "pn2_group_max_f32")
+    torch.cuda.synchronize()
+    want, want_arg = tr.group_max(a, K)
+    assert want_arg[0, 0] == 0 and want_arg[G - 1, C - 1] == 0 and np.isnan(want[0, 0])
+    np.testing.assert_array_equal(arg.cpu().numpy(), want_arg)
+    np.testing.assert_array_equal(take_rows(out, C, "max").view(np.int32), want.view(np.int32))

@@ -36,6 +36,20 @@ def test_public_names_and_signatures():
         "point_number", "sample_number_list", "radius_list", "in_channel", "mlp_list", "num_category"]
 
 
+def test_train_launches_go_through_ops():
+    """pn2/train.py makes no native call of its own (every launch is an ops.*_direct function,
+    which ops.kernel_timer sees), and the package has one workspace cache, in ops."""
+    def source(name):
+        with open(os.path.join(PKG, "pn2", name)) as f:
+            return f.read()
+    train, ops = source("train.py"), source("ops.py")
+    for text in ("_lib.check(", ".data_ptr()", "_stream", "import _lib", "_WS", "_workspace"):
+        assert text not in train, text
+    for text in ("_GEMM_WS", "_gemm_workspace"):
+        assert text not in ops, text
+    assert ops.count("\n_WS = {}") == 1
+
+
 @pytest.mark.parametrize("name", golden_names("head_"))
 def test_heads_rebuild_reference_weights(name):
     """pn2.heads consume the RNG exactly like the reference heads: same seeded state_dict
