@@ -42,6 +42,8 @@
  *                          the heads' Linear + BatchNorm1d + ReLU under autograd, forward and
  *                          backward, each sum in a fixed order   model/pointnet2_cls_ssg.py:31-36;
  *                                                            translation_ssg.py:23-26
+ *   pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32
+ *                          the same for batches above 64 rows (the scripts' --batch_size)
  *   pn2_bn_train_stats_f32 / pn2_bn_relu_apply_f32 (/ pn2_bn_train_forward_f32: both) /
  *   pn2_group_max_f32 / pn2_bn_relu_backward_f32
  *                          train-mode BatchNorm2d + ReLU + torch.max over K, forward and backward
@@ -385,6 +387,39 @@ int pn2_fc_bn_backward_f32(const float *dA, int64_t ldd, const float *Y, int64_t
                            int64_t B, int64_t N, int64_t K,
                            float *dY, int64_t ldyy, float *dW, int64_t ldw, float *dbias,
                            float *dgamma, float *dbeta, int flags, void *stream);
+
+/* ---- the same layer for any number of rows (csrc/fc_train.hip, the slab kernels):
+ * pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 take the argument lists of
+ * pn2_fc_bn_forward_f32 / pn2_fc_bn_backward_f32, name for name, and serve 1 <= B <= 2^30.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * The whole contract above applies: the meaning of every output and flag, THE ORDER RULES 1-4
+ * as written (none of them names a row limit), the leading dimensions, 16-byte loads only where
+ * base and leading dimension allow, no load past an edge, and the same PN2_EINVAL cases before
+ * any device call (batch statistics with B == 1 included).  What the rules mean above 64 rows:
+ *   1. a row of Y is the same fma chain over k whatever B is: rows of Y equal, bit for bit,
+ *      what either forward entry gives for any subset of the rows of X;
+ *   2. s, q, dbeta, dgamma and dbias stay ONE float64 chain over r = 0 .. B-1 per column, an
+ *      element of dW ONE float32 fma chain over r = 0 .. B-1: a column's rows are never split
+ *      over lanes or workgroups and no partial sums are combined.  A workgroup owns 4 columns
+ *      and walks all B rows of them in slabs of pn2_fc_train_max_rows() rows, carrying its
+ *      accumulators from slab to slab in row order -- so the launch has ceil(N/4) workgroups
+ *      whatever B is, and its time grows with B;
+ *   3., 4. no float atomics, no wait for another workgroup, no workspace.
+ * For B <= pn2_fc_train_max_rows() the results are bit for bit those of the entries above.
+ * With batch statistics the forward reads its own Y back to write A: Y and A must not overlap
+ * (as above).  PN2_EUNSUPPORTED for B > 2^30 (the kernels count rows in an int32). */
+int pn2_fc_bn_forward_rows_f32(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias,
+                               int64_t B, int64_t N, int64_t K, double eps, double momentum,
+                               float *running_mean, float *running_var,
+                               const float *gamma, const float *beta,
+                               float *Y, int64_t ldy, float *A, int64_t lda,
+                               float *stats /* [mean | invstd], 2N */, int flags, void *stream);
+int pn2_fc_bn_backward_rows_f32(const float *dA, int64_t ldd, const float *Y, int64_t ldy,
+                                const float *X, int64_t ldx, const float *stats,
+                                const float *gamma, const float *beta,
+                                int64_t B, int64_t N, int64_t K,
+                                float *dY, int64_t ldyy, float *dW, int64_t ldw, float *dbias,
+                                float *dgamma, float *dbeta, int flags, void *stream);
 
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]

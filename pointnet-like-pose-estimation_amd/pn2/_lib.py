@@ -109,6 +109,10 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp]),
     "pn2_fc_bn_backward_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
                                       _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp]),
+    "pn2_fc_bn_forward_rows_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _dbl, _dbl, _vp, _vp,
+                                          _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp]),
+    "pn2_fc_bn_backward_rows_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
+                                           _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

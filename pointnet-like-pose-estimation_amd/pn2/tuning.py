@@ -52,8 +52,18 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      and group_backward=1 a PointNet++ head's train step then has no
                      order-dependent sum in any kernel of this project (dropout's mask, the
                      loss and the optimizer stay torch).  Batches above
-                     pn2_fc_train_max_rows() rows keep the modules.  0 or 1; anything else is
-                     an error
+                     pn2_fc_train_max_rows() rows keep the modules unless train_head_rows=1.
+                     0 or 1; anything else is an error
+    train_head_rows  with train_head=1 only.  0: an FC layer whose batch has more than
+                     pn2_fc_train_max_rows() (64) rows stays the torch modules, so above 64 rows
+                     the reproducibility route above does not hold; 1: such a batch runs
+                     pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 (+ pn2_gemm_nn_f32),
+                     the same sums in the same fixed orders at any number of rows -- each
+                     column's rows are one serial chain inside one workgroup, so these launches
+                     have no more workgroups than at 64 rows and their time grows with the
+                     batch (DESIGN.md §4.4 has the measurements).  Batches of 64 rows or fewer
+                     run the 64-row kernels either way; with train_head=0 the key does nothing.
+                     0 or 1; anything else is an error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -84,9 +94,10 @@ HOST_DEFAULTS = {
     "group_backward": 0,
     "train_gemm": 0,
     "train_head": 0,
+    "train_head_rows": 0,
 }
 # host keys with a checked range (inclusive); the others take any integer
-HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1)}
+HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1), "train_head_rows": (0, 1)}
 
 
 def _check_host(key, value):

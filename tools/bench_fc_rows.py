@@ -1,0 +1,150 @@
+"""The heads' FC layers under autograd above 64 rows: what train_head=1 runs there without
+train_head_rows (the torch modules: library GEMMs, BatchNorm1d's kernels, ReLU and their
+backward) against pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 + pn2_gemm_nn_f32
+(train_head_rows=1, csrc/fc_train.hip's slab kernels), on identical inputs.
+
+  tail      the ClsSSG FC tail 1024 -> 512 -> 256 -> 7 forward + backward in train mode, at
+            B = 128 and B = 256 rows; and each launch's own time in one forward + backward
+            (ops.kernel_timer), in launch order: which layer and direction the time goes to
+  mean_mlp  the TranslationSSG mean MLP 3 -> 6 -> 3 forward + backward, B = 128 and 256
+  step      the whole ClsSSG train step at B = 128 clouds of 1024 points (forward, nll_loss,
+            backward, SGD step) with train_gemm=1, group_backward=1, train_head=1, at
+            train_head_rows 0 / 1
+
+The route buys reproducibility; no ratio is required of it.  Method, as tools/bench_fc_train.py:
+HIP events around `reps` back-to-back calls after `warmup` calls, the routes interleaved within
+each of `rounds` rounds, median (min, max) of the rounds; step: wall clock over 20 synchronised
+steps after 3.  ratio = modules median / kernels median (> 1: the kernels are faster).
+Needs a ROCm device.  Writes one JSON document (default profiles/fc_rows/timing.json) and
+prints it."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
+                os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
+import cases  # noqa: E402
+from bench_fc_train import REPRO, interleaved, summary  # noqa: E402
+from pn2 import heads as H  # noqa: E402
+from pn2 import ops, tuning  # noqa: E402
+
+MODULES = {"train_head": 1, "train_head_rows": 0}
+KERNELS = {"train_head": 1, "train_head_rows": 1}
+
+
+def two_routes(fn, a):
+    ms = interleaved({"modules": (MODULES, fn), "kernels": (KERNELS, fn)}, a)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"ms": {k: summary(v) for k, v in ms.items()},
+            "ratio_modules_over_kernels": round(med["modules"] / med["kernels"], 3)}
+
+
+def launches(fn):
+    """One call under the kernel route -> [[name, ms], ...] in launch order."""
+    with tuning.override(**KERNELS), ops.kernel_timer() as t:
+        fn()
+    torch.cuda.synchronize()
+    return [[r[0], round(r[1].elapsed_time(r[2]), 4)] for r in t.records]
+
+
+def bench_tail(B, a):
+    torch.manual_seed(0)
+    model = H.ClsSSG().cuda().train()
+    x = torch.randn(B, 1024, generator=torch.Generator().manual_seed(1)).cuda().requires_grad_(True)
+    R = torch.randn(B, 7, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def fwd_bwd():
+        model.zero_grad(set_to_none=True)
+        x.grad = None
+        model._fc(x).backward(R)
+
+    return {"B": B, "chain": [1024, 512, 256, 7], "forward_backward": two_routes(fwd_bwd, a),
+            "launch_ms_one_forward_backward": launches(fwd_bwd)}
+
+
+def bench_mean_mlp(B, a):
+    torch.manual_seed(0)
+    model = H.TranslationSSG().cuda().train()
+    x = torch.randn(B, 3, generator=torch.Generator().manual_seed(3)).cuda().requires_grad_(True)
+    R = torch.randn(B, 3, generator=torch.Generator().manual_seed(4)).cuda()
+
+    def fwd_bwd():
+        model.zero_grad(set_to_none=True)
+        x.grad = None
+        model._mean_mlp(x).backward(R)
+
+    return {"B": B, "chain": [3, 6, 3], "forward_backward": two_routes(fwd_bwd, a),
+            "launch_ms_one_forward_backward": launches(fwd_bwd)}
+
+
+def bench_step(B, a):
+    x = cases.cloud("uniform3", B, 1024, 5).permute(0, 2, 1).contiguous().cuda()
+    y = (torch.arange(B) % 7).cuda()
+    torch.manual_seed(0)
+    model = H.ClsSSG().cuda().train()
+    opt = torch.optim.SGD(model.parameters(), lr=1e-3, momentum=0.9)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        logp, _, _ = model(x)
+        F.nll_loss(logp, y).backward()
+        opt.step()
+
+    def run(keys):
+        with tuning.override(**keys):
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                step()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / 20 * 1e3
+
+    routes = {"train_head_rows=0": dict(REPRO, train_head_rows=0), "train_head_rows=1": dict(REPRO, train_head_rows=1)}
+    ms = {k: [] for k in routes}
+    for _ in range(a.rounds):
+        for k, keys in routes.items():
+            ms[k].append(run(keys))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"model": "ClsSSG", "B": B, "N": 1024, "keys": "train_gemm=1,group_backward=1,train_head=1",
+            "ms_per_step": {k: summary(v) for k, v in ms.items()},
+            "ratio_modules_over_kernels": round(med["train_head_rows=0"] / med["train_head_rows=1"], 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fc_rows", "timing.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_fc_rows: needs a ROCm device")
+    doc = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "rounds": a.rounds, "warmup": a.warmup,
+           "max_rows": ops.fc_train_max_rows(),
+           "protocol": "HIP events around `reps` back-to-back calls per route (identical inputs), after "
+                       "`warmup` calls; routes interleaved within each of `rounds` rounds; median (min, "
+                       "max) of the rounds; modules = train_head=1 alone (the torch modules above max_rows "
+                       "rows), kernels = train_head=1,train_head_rows=1; ratio = modules median / kernels "
+                       "median.  step: wall clock over 20 synchronised train steps after 3, the routes "
+                       "interleaved",
+           "tail": {"B=%d" % B: bench_tail(B, a) for B in (128, 256)},
+           "mean_mlp": {"B=%d" % B: bench_mean_mlp(B, a) for B in (128, 256)},
+           "step": bench_step(128, a)}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    text = json.dumps(doc, indent=1) + "\n"
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
