@@ -171,6 +171,24 @@ int pn2_fps_host_ws_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64
                         float *out_pts, float *out_packed, float *pts_packed, void *workspace,
                         int64_t workspace_bytes, void *stream);
 
+/* ---- two consecutive sampling levels in one launch (csrc/fps_body.h fps2_block): level 1
+ * samples S1 of the N input points, level 2 samples S2 of level 1's centroids.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * What pn2_fps_f32(pts, ..., start1, S1, out_idx1, out_pts1, out_packed1, pts_packed1) followed by
+ * pn2_fps_f32(out_pts1 [B,S1,3] contiguous, ..., start2, S2, out_idx2, out_pts2, out_packed2,
+ * pts_packed2) write, bit for bit; out_idx1 / out_idx2 required, the others may be NULL.
+ * start1[B] in [0, N), start2[B] in [0, S1): int64, device.  One workgroup per cloud; level 2
+ * runs on the ceil(S1 / 128) waves it needs, from level 1's records in LDS.
+ * pn2_fps2_eligible(N, C, S1, S2): 1 when the shape is taken -- C == 3, N <= 1024, S1 <= 512,
+ * S2 <= 8192 and the automatic FPS block choice (tuning fps_threads = fps_ppt = 0, fps_mid = 512)
+ * -- else 0, and pn2_fps2_f32 returns PN2_EUNSUPPORTED: the caller runs the two launches. */
+int pn2_fps2_eligible(int64_t N, int64_t C, int64_t S1, int64_t S2);
+int pn2_fps2_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
+                 int64_t sc, const int64_t *start1, int64_t S1, const int64_t *start2, int64_t S2,
+                 int64_t *out_idx1, float *out_pts1, float *out_packed1, float *pts_packed1,
+                 int64_t *out_idx2, float *out_pts2, float *out_packed2, float *pts_packed2,
+                 void *stream);
+
 /* ---- farthest-point downsampling of raw clouds by the reference's NUMPY rule
  * (provider.py:183-204 and its copies; csrc/fps_points.hip), a ragged batch in one launch.
  * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.

@@ -34,6 +34,13 @@ __global__ __launch_bounds__(NT) void fps_kernel(const FpsArgs F) {
     fps_block<NT, PPT, CM, FIXED, LDSC, CR>(F, (int)blockIdx.x, fsm);
 }
 
+// both sampling levels of a cloud by one workgroup (fps_body.h fps2_block)
+template <int NT>
+__global__ __launch_bounds__(NT) void fps2_kernel(const Fps2Args G) {
+    extern __shared__ __attribute__((aligned(16))) float fsm[];
+    fps2_block<NT>(G, (int)blockIdx.x, fsm);
+}
+
 // ------------------------------------------------------------------------- streamed FPS
 // Any N and S: nothing of the cloud is register-resident.  Each iteration every thread walks
 // the points n = tid, tid + NT, ... (coalesced reads of the input for either layout), computes
@@ -391,6 +398,53 @@ extern "C" int pn2_fps_f32(const float *pts, int64_t B, int64_t N, int64_t C, in
                            void *stream) {
     return pn2_fps_ws_f32(pts, B, N, C, sb, sn, sc, start, S, out_idx, out_pts, out_packed, pts_packed, nullptr, 0,
                           stream);
+}
+
+// ------------------------------------------------------------------------- two-level FPS
+// The shapes fps2_kernel takes: xyz clouds of up to kFps2MaxN points, S1 <= kFps2MaxS1, under the
+// automatic 512 x 2 / 256 x 2 block choice (a forced block shape, or the fused pipelines' 256 x 4
+// profile, keeps the two launches those were measured with).
+extern "C" int pn2_fps2_eligible(int64_t N, int64_t C, int64_t S1, int64_t S2) {
+    const Tuning T = tuning();
+    return C == 3 && N >= 1 && N <= kFps2MaxN && S1 >= 1 && S1 <= kFps2MaxS1 && S2 >= 1 && S2 <= kFpsMaxS &&
+           T.fps_threads == 0 && T.fps_ppt == 0 && T.fps_mid == 512;
+}
+
+extern "C" int pn2_fps2_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
+                            int64_t sc, const int64_t *start1, int64_t S1, const int64_t *start2,
+                            int64_t S2, int64_t *out_idx1, float *out_pts1, float *out_packed1,
+                            float *pts_packed1, int64_t *out_idx2, float *out_pts2, float *out_packed2,
+                            float *pts_packed2, void *stream) {
+    PN2_REQUIRE(pts && start1 && start2 && out_idx1 && out_idx2, "pn2_fps2_f32: null pointer");
+    PN2_REQUIRE(B >= 0 && N >= 1 && C >= 1 && S1 >= 1 && S2 >= 1,
+                "pn2_fps2_f32: bad shape B=%lld N=%lld C=%lld S1=%lld S2=%lld", (long long)B, (long long)N,
+                (long long)C, (long long)S1, (long long)S2);
+    if (!pn2_fps2_eligible(N, C, S1, S2))
+        return set_error(PN2_EUNSUPPORTED,
+                         "pn2_fps2_f32: N=%lld C=%lld S1=%lld S2=%lld is not a two-level shape "
+                         "(pn2_fps2_eligible): run two pn2_fps_f32 launches",
+                         (long long)N, (long long)C, (long long)S1, (long long)S2);
+    if (B == 0) return PN2_OK;
+    FpsStart fs;
+    fs.dev = start1;
+    Fps2Args G;
+    G.l1 = fps_args(pts, N, C, sb, sn, sc, fs, S1, out_idx1, out_pts1, out_packed1, pts_packed1);
+    G.start2 = start2;
+    G.S2 = (int)S2;
+    G.out_idx2 = out_idx2;
+    G.out_pts2 = out_pts2;
+    G.out_packed2 = out_packed2;
+    G.pts_packed2 = pts_packed2;
+    hipStream_t st = as_stream(stream);
+    if (N <= 512) {
+        const size_t lds = fps2_block_lds(256, N, S1, S2);
+        hipLaunchKernelGGL(fps2_kernel<256>, dim3((unsigned)B), dim3(256), lds, st, G);
+    } else {
+        const size_t lds = fps2_block_lds(512, N, S1, S2);  // <= 59 KB at the caps
+        hipLaunchKernelGGL(fps2_kernel<512>, dim3((unsigned)B), dim3(512), lds, st, G);
+    }
+    PN2_LAUNCH_CHECK("fps2_kernel");
+    return PN2_OK;
 }
 
 #ifdef PN2_FPS_STAMPS

@@ -395,4 +395,131 @@ __device__ __forceinline__ void fps_block(const FpsArgs &F, const int b, float *
     }
 }
 
+// ------------------------------------------------------------------- two sampling levels
+// Both FPS levels of a cloud by one workgroup (csrc/fps.hip fps2_kernel): level 1 samples S1 of
+// the N input points (fps_block, unchanged), level 2 samples S2 of those S1 centroids -- what a
+// second launch over level 1's out_pts computes, bit for bit, without the launch and without
+// re-reading the centroids from memory.  xyz clouds, two points per lane.
+struct Fps2Args {
+    FpsArgs l1;             // level 1, start in l1.start.dev
+    const int64_t *start2;  // [B] level 2's start draws (device)
+    int S2;
+    int64_t *out_idx2;      // [B,S2]; out_pts2 [B,S2,3], out_packed2 [B,S2,4], pts_packed2 [B,S1,4]
+    float *out_pts2, *out_packed2, *pts_packed2;
+};
+
+constexpr int kFps2MaxN = 1024, kFps2MaxS1 = 512;  // level 1 at <= 512 x 2, level 2 at <= 256 x 2
+
+// LDS floats of level 1 (fps_block<NT, 2, 3, true, true>'s own layout), then level 2's: S2
+// indices, the key words, the S1 packed records
+__host__ __device__ inline size_t fps2_block_lds(int NT, int64_t N, int64_t S1, int64_t S2) {
+    return fps_block_lds(NT, 3, true, N, S1) + (size_t)((S2 + 3) & ~3) * 4 + kFpsKeyRegion + (size_t)S1 * 16;
+}
+
+template <int NT>
+__device__ __forceinline__ void fps2_block(const Fps2Args &G, const int b, float *fsm) {
+#pragma clang fp contract(off)
+    const FpsArgs &F = G.l1;
+    fps_block<NT, 2, 3, true, true>(F, b, fsm);
+    // fps_block's LDS after its last barrier: the S1 chosen indices and the cloud copy
+    const int N = F.N, S1 = F.S, S2 = G.S2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int *sidx1 = reinterpret_cast<const int *>(fsm);
+    const float *cloud = fsm + ((S1 + 3) & ~3) + kFpsKeyRegion / 4;  // [N][4]
+    float *l2 = fsm + fps_block_lds(NT, 3, true, N, S1) / 4;
+    int *sidx = reinterpret_cast<int *>(l2);                                              // [S2]
+    unsigned long long *key = reinterpret_cast<unsigned long long *>(l2 + ((S2 + 3) & ~3));  // [3]
+    float *rec = l2 + ((S2 + 3) & ~3) + kFpsKeyRegion / 4;                                  // [S1][4]
+
+    // ---- level 2's points: the packed records of level 1's centroids (coordinates and the
+    // contiguous-layout ssq, as level 1 wrote them to out_packed and a second launch would
+    // write them to its pts_packed), built once from the cloud copy -- nothing is added to
+    // level 1's loop
+    for (int i = tid; i < S1; i += NT) {
+        const int n = sidx1[i];
+        float p[3], sq[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p[k] = cloud[n * 4 + k];
+            sq[k] = mul_rn(p[k], p[k]);
+        }
+        const float4 r = make_float4(p[0], p[1], p[2], contig_sum<3>(sq, 3));
+        *reinterpret_cast<float4 *>(rec + i * 4) = r;
+        if (G.pts_packed2) *reinterpret_cast<float4 *>(G.pts_packed2 + ((int64_t)b * S1 + i) * 4) = r;
+    }
+    if (tid < 3) key[tid] = 0ull;
+    __syncthreads();
+    // The waves level 2 needs at two points per lane run its loop.  The others would hold only
+    // padding points, which never win: they stay out of the exchange (no distances, no key
+    // atomic, no key read) and only arrive at each iteration's barrier, then at the last one.
+    const int nw = (S1 + 127) >> 7;
+    if (wave >= nw) {
+        if (nw > 1)
+            for (int i = 0; i < S2 - 1; ++i) __syncthreads();
+        __syncthreads();
+        return;
+    }
+
+    pn2_f2 q[3];
+    unsigned dist[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = tid * 2 + j;
+        const bool valid = n < S1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q[k][j] = valid ? rec[n * 4 + k] : 0.f;
+        dist[j] = valid ? __float_as_uint(1e10f) : 0u;
+    }
+    int far = (int)G.start2[b];
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = rec[far * 4 + k];
+    for (int i = 0;; ++i) {
+        if (tid == 0) sidx[i] = far;
+        if (i == S2 - 1) break;
+        pn2_f2 sq[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const pn2_f2 d = q[k] - c[k];
+            sq[k] = d * d;
+        }
+        const pn2_f2 dd = seq_sum<3>(sq, 3);
+        dist[0] = min(dist[0], __float_as_uint(dd.x));
+        dist[1] = min(dist[1], __float_as_uint(dd.y));
+        const unsigned bv = max(dist[0], dist[1]);
+        const unsigned wv = wave_max_u32(bv);
+        const int ol = (int)__builtin_ctzll(__ballot(bv == wv));
+        const int bj = ((__ballot(dist[0] == wv) >> ol) & 1ull) ? 0 : 1;
+        if (nw == 1) {
+            far = ol * 2 + bj;
+        } else {
+            // fps_block's exchange: key[i%3] is reset one iteration ahead, its last reader
+            // passed the previous barrier
+            if (lane == ol) {
+                const unsigned idx = (unsigned)(tid * 2 + bj);
+                atomicMax(&key[i % 3], ((unsigned long long)wv << 32) | (0xFFFFFFFFu - idx));
+            }
+            if (tid == 64) key[(i + 1) % 3] = 0ull;
+            __syncthreads();
+            far = __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - (unsigned)key[i % 3]));
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = rec[far * 4 + k];
+    }
+    __syncthreads();
+
+    for (int i = tid; i < S2; i += nw * 64) {
+        const int n = sidx[i];
+        const float4 r = *reinterpret_cast<const float4 *>(rec + n * 4);
+        G.out_idx2[(int64_t)b * S2 + i] = n;
+        if (G.out_pts2) {
+            float *o = G.out_pts2 + ((int64_t)b * S2 + i) * 3;
+            o[0] = r.x;
+            o[1] = r.y;
+            o[2] = r.z;
+        }
+        if (G.out_packed2) *reinterpret_cast<float4 *>(G.out_packed2 + ((int64_t)b * S2 + i) * 4) = r;
+    }
+}
+
 }  // namespace pn2

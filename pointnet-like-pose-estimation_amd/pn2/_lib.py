@@ -84,6 +84,9 @@ SIGNATURES = {
                               _i64, _vp]),
     "pn2_fps_host_ws_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                                    _vp, _i64, _vp]),
+    "pn2_fps2_eligible": (_int, [_i64, _i64, _i64, _i64]),
+    "pn2_fps2_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_fps_points_workspace_bytes": (_i64, [_int, _i64, _i64]),
     "pn2_fps_points": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64,
                               _vp]),

@@ -197,6 +197,46 @@ def _(points, npoint, start):
     return (e(B, npoint, dtype=torch.int64), e(B, npoint, C), e(B, npoint, cp), e(B, N, cp))
 
 
+def fps2_eligible(N: int, C: int, S1: int, S2: int) -> bool:
+    """Whether two consecutive sampling levels (N -> S1 -> S2 points of C channels) run as one
+    pn2_fps2_f32 launch under the current tuning (include/pn2.h)."""
+    return bool(_L.pn2_fps2_eligible(N, C, S1, S2))
+
+
+last_fps2_path = None  # what the last fps2_direct call ran: "two_level" or "separate"
+
+
+def fps2_direct(points: Tensor, npoint1: int, npoint2: int, start1: Tensor, start2: Tensor):
+    """Two consecutive sampling levels: fps_direct(points, npoint1, start1) and fps_direct(its
+    new_points, npoint2, start2) -> both result tuples, bit for bit.  Eligible shapes
+    (fps2_eligible) run as one launch, one workgroup per cloud doing both levels; any other
+    shape runs the two launches.  `last_fps2_path` names the path taken."""
+    global last_fps2_path
+    _dev(points, "pn2::fps2")
+    B, N, C = points.shape
+    if not fps2_eligible(N, C, npoint1, npoint2):
+        last_fps2_path = "separate"
+        r1 = fps_direct(points, npoint1, start1)
+        return r1, fps_direct(r1[1], npoint2, start2)
+    dev = points.device
+    start1 = start1.to(device=dev, dtype=torch.int64).contiguous()
+    start2 = start2.to(device=dev, dtype=torch.int64).contiguous()
+    cp = packed_stride(C)
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    idx1 = torch.empty(B, npoint1, dtype=torch.int64, device=dev)
+    idx2 = torch.empty(B, npoint2, dtype=torch.int64, device=dev)
+    newp1, cpk1, ppk1 = e(B, npoint1, C), e(B, npoint1, cp), e(B, N, cp)
+    newp2, cpk2, ppk2 = e(B, npoint2, C), e(B, npoint2, cp), e(B, npoint1, cp)
+    sb, sn, sc = points.stride()
+    _run("pn2_fps2_f32", _L.pn2_fps2_f32,
+         (points.data_ptr(), B, N, C, sb, sn, sc, start1.data_ptr(), npoint1, start2.data_ptr(), npoint2,
+          idx1.data_ptr(), newp1.data_ptr(), cpk1.data_ptr(), ppk1.data_ptr(),
+          idx2.data_ptr(), newp2.data_ptr(), cpk2.data_ptr(), ppk2.data_ptr(), _stream(points)), dev,
+         flops=float(B) * (npoint1 * N + npoint2 * npoint1) * (3 * C + 2))
+    last_fps2_path = "two_level"
+    return (idx1, newp1, cpk1, ppk1), (idx2, newp2, cpk2, ppk2)
+
+
 # ------------------------------------------------------------------------------ pack_points
 def pack_points_direct(points: Tensor) -> Tensor:
     """[B,N,C] (any strides) -> [B,N,cp] records (coords, ssq in the reference's order, pad)."""

@@ -210,6 +210,7 @@ class PipelinedForward:
         self.sas = self._find_sas()
         self.launch_batch = 128  # clouds per launch (_profile); GraphedPipeline.run sets it
         self.geometry_bq = None  # ball queries on the geometry stream; None: tuning geometry_bq
+        self.fps_paths = []  # _fps_chain's last call: "two_level" / "separate" per chain
 
     def _find_sas(self):
         return [m for m in self.model.modules()
@@ -288,6 +289,7 @@ class PipelinedForward:
                 starts[id(sa)] = shard.device_start(B, n, dev)
                 n = sa.point_number
         entries = {}
+        self.fps_paths = []  # per chain, how its first two levels were sampled (this call)
         # geometry_bq = 0: the ball queries run in each batch's forward instead (the module
         # queries when its entry holds no lists), leaving the FPS alone on the geometry stream
         bq = bool(tuning.get("geometry_bq") if self.geometry_bq is None else self.geometry_bq)
@@ -306,10 +308,21 @@ class PipelinedForward:
                 first[i] = (newp[i * B:(i + 1) * B], cpk[i * B:(i + 1) * B], ppk[i * B:(i + 1) * B])
         for i, ch in enumerate(chains):
             p = pts
+            second = None  # the chain's second layer, sampled in its first layer's launch
+            # single-scale layers only: the MSG heads keep their two launches
+            if i not in first and len(ch) > 1 and \
+                    not any(isinstance(sa, PointNetSetAbstractionMsg) for sa in ch[:2]) and \
+                    ops.fps2_eligible(N, p.shape[2], ch[0].point_number, ch[1].point_number):
+                r1, r2 = ops.fps2_direct(p, ch[0].point_number, ch[1].point_number,
+                                         starts[id(ch[0])], starts[id(ch[1])])
+                first[i], second = r1[1:], r2[1:]
+            self.fps_paths.append("separate" if second is None else "two_level")
             for j, sa in enumerate(ch):
                 C = p.shape[2]
                 if j == 0 and i in first:
                     newp, cpk, ppk = first[i]
+                elif j == 1 and second is not None:
+                    newp, cpk, ppk = second
                 else:
                     _, newp, cpk, ppk = ops.fps_direct(p, sa.point_number, starts[id(sa)])
                 if not bq:
