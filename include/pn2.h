@@ -439,6 +439,102 @@ int pn2_fc_bn_backward_rows_f32(const float *dA, int64_t ldd, const float *Y, in
                                 float *dY, int64_t ldyy, float *dW, int64_t ldw, float *dbias,
                                 float *dgamma, float *dbeta, int flags, void *stream);
 
+/* ---- the reductions after the heads' last layer, and the loops' metrics (csrc/loss.hip):
+ * log_softmax under autograd, the four criteria of the get_loss classes, and the test loops'
+ * per-class bookkeeping accumulated on the device.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * Reference: the get_loss classes of model/pointnet2_cls_ssg.py:40-47 (F.nll_loss),
+ * rotation_ssg.py:40-50 (nn.MSELoss / nn.L1Loss, reduction 'mean' or 'sum') and
+ * sign_ssg.py:38-45 (nn.BCELoss); F.log_softmax at pointnet2_cls_ssg.py:36; the bookkeeping of
+ * train_classification.py:121-122, 144-150, train_rotation.py:126-127, 157-163 and
+ * train_sign.py:148-153.
+ * float32 matrices are row-major with a leading dimension (>= the width), read and written in
+ * place through it; targets are int64 where the reference's are.  Every call is async on the
+ * caller's stream and uses no workspace.  The unit is compiled without contraction: every
+ * operation below rounds on its own; exp and log are float64 library functions, everything else
+ * is an IEEE operation.
+ *
+ * pn2_log_softmax_rows_f32: X [B][K] -> Y [B][K], 1 <= K <= 1024, 1 <= B <= 2^30.  Per row,
+ *   independent of every other row and of B:
+ *     m = max_j x_j;  s = sum_j exp(double(x_j) - double(m)) in ascending j from +0.0, in
+ *     float64;  y_j = float32((double(x_j) - double(m)) - log(s)).
+ * pn2_log_softmax_rows_backward_f32: dY, the forward's Y -> dX:
+ *     g = sum_j double(dy_j) in ascending j from +0.0;
+ *     dx_j = float32(double(dy_j) - exp(double(y_j)) * g).
+ *
+ * pn2_criterion_forward_f32: P [B][K] float32, kind PN2_LOSS_*, reduction PN2_REDUCE_* -> one
+ *   float32 at `loss`.  target: int64 [B] for PN2_LOSS_NLL (ldt is not read), float32 [B][K]
+ *   (leading dimension ldt) otherwise.  Element terms, in float64 from the float32 inputs:
+ *     NLL  -P[b][t_b]                                          (one term per row)
+ *     MSE  d*d,  d = double(p) - double(t)
+ *     L1   |d|
+ *     BCE  -(t*max(log(p), -100) + (1-t)*max(log(1-p), -100))   (torch's clamp; p is not
+ *          checked to lie in [0, 1]: outside it the term is NaN)
+ *   THE ORDER RULE: the loss is ONE float64 chain acc = acc + term over the terms in row-major
+ *   order (b ascending, then j ascending) from +0.0.  PN2_REDUCE_SUM rounds the chain to
+ *   float32 once; PN2_REDUCE_MEAN divides it in float64 by the term count (B for NLL, B*K
+ *   otherwise) and rounds once.  No float atomics; no partial sums exist, so none are combined:
+ *   the launch is one workgroup whose threads compute the terms side by side, and only the adds
+ *   are ordered.  The serial chain is an accepted cost (B*K is a few thousand for every
+ *   reference shape), as in the slab kernels above.
+ * pn2_criterion_backward_f32: the same arguments, g a DEVICE pointer to the upstream float32
+ *   scalar -> dP [B][K] = float32((double(g)*c)*term'), c = 1 (sum) or 1.0/count (mean) in
+ *   float64, the products in that order in float64, rounded once.  term':
+ *     NLL  -1 at the target column, 0 elsewhere; the whole row is written
+ *     MSE  2*d
+ *     L1   sign(d): 1, -1, or 0 at d == 0
+ *     BCE  (p - t) / max((1 - p)*p, 1e-12)
+ *   An NLL target outside [0, K): the forward's term is NaN (the loss is NaN), the backward
+ *   writes +0 to the whole row; nothing is read or written with that index.
+ *
+ * pn2_meter_update: ONE launch per batch adds that batch to device-resident float64 state:
+ *   acc [num_category][W], one `invalid` count, and the batch's record at records[slot*RW ..]
+ *   (records holds `slots` records; the host passes the index).  Kinds:
+ *     PN2_METER_CLS   pred, target int64 [B] (ldp, ldt, label not read; the category of a row
+ *       is its target), W = 2, RW = 1.  For every category c present in the batch:
+ *       acc[c][0] += double(correct_c)/double(count_c), acc[c][1] += 1.
+ *       record = double(correct)/double(B).
+ *     PN2_METER_SIGN  pred, target float32 [B] with strides ldp, ldt, label int64 [B], W = 2,
+ *       RW = 1: acc[c][0] += correct_c, acc[c][1] += count_c; record = correct/B.  A row is
+ *       correct when pred == target as floats.
+ *     PN2_METER_POSE  pred, target float32 [B][D], label int64 [B], W = 1 + D, RW = D:
+ *       a = |p - t|, one float32 subtraction.  Per category present and per axis: the float64
+ *       chain of a over that category's rows in row order from +0.0, divided by the count,
+ *       rounded to float32, then added to acc[c][1+axis]; acc[c][0] += 1.  record[axis] = the
+ *       same float32 mean over all B rows.
+ *   D is 1 for CLS and SIGN.  A category absent from the batch keeps its row's bits.  A label
+ *   outside [0, num_category) is skipped -- nothing is indexed with it -- and counted in
+ *   invalid[0]; the records count every row.  One workgroup: a thread per (category, column),
+ *   per record column and for the invalid count walks the rows in order.  Two updates of one
+ *   state must be ordered on one stream.
+ *
+ * Errors, before any device call: PN2_EINVAL for B < 1, K < 1 (D < 1, num_category < 1), a
+ * leading dimension below its width, a NULL required pointer, an unknown kind or reduction, D
+ * != 1 for CLS / SIGN, a slot outside [0, slots); PN2_EUNSUPPORTED for B > 2^30 (rows are
+ * counted in an int32), log_softmax with K > 1024, a criterion with K > 2^30, a meter with
+ * D > 16 or num_category > 4096. */
+#define PN2_LOSS_NLL 0
+#define PN2_LOSS_MSE 1
+#define PN2_LOSS_L1 2
+#define PN2_LOSS_BCE 3
+#define PN2_REDUCE_MEAN 0
+#define PN2_REDUCE_SUM 1
+#define PN2_METER_CLS 0
+#define PN2_METER_SIGN 1
+#define PN2_METER_POSE 2
+int pn2_log_softmax_rows_f32(const float *X, int64_t ldx, float *Y, int64_t ldy, int64_t B, int64_t K,
+                             void *stream);
+int pn2_log_softmax_rows_backward_f32(const float *dY, int64_t ldd, const float *Y, int64_t ldy, float *dX,
+                                      int64_t ldx, int64_t B, int64_t K, void *stream);
+int pn2_criterion_forward_f32(int kind, int reduction, const float *P, int64_t ldp, const void *target,
+                              int64_t ldt, int64_t B, int64_t K, float *loss, void *stream);
+int pn2_criterion_backward_f32(int kind, int reduction, const float *P, int64_t ldp, const void *target,
+                               int64_t ldt, const float *g, int64_t B, int64_t K, float *dP, int64_t ldd,
+                               void *stream);
+int pn2_meter_update(int kind, const void *pred, int64_t ldp, const void *target, int64_t ldt,
+                     const int64_t *label, int64_t B, int64_t D, int64_t num_category, double *acc,
+                     double *invalid, double *records, int64_t slot, int64_t slots, void *stream);
+
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]
  * such that layer(x) = relu(alpha * (W x) + beta): the eval-mode BatchNorm2d folded with the

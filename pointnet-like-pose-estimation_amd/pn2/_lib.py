@@ -72,6 +72,9 @@ DTYPE_F32 = 0
 DTYPE_F64 = 1
 INDEX_I64 = 0
 INDEX_I32 = 1
+LOSS_NLL, LOSS_MSE, LOSS_L1, LOSS_BCE = 0, 1, 2, 3
+REDUCE_MEAN, REDUCE_SUM = 0, 1
+METER_CLS, METER_SIGN, METER_POSE = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol include/pn2.h declares
 SIGNATURES = {
@@ -116,6 +119,12 @@ SIGNATURES = {
                                           _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp]),
     "pn2_fc_bn_backward_rows_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
                                            _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp]),
+    "pn2_log_softmax_rows_f32": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "pn2_log_softmax_rows_backward_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "pn2_criterion_forward_f32": (_int, [_int, _int, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "pn2_criterion_backward_f32": (_int, [_int, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "pn2_meter_update": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
+                                _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

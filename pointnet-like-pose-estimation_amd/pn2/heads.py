@@ -29,6 +29,7 @@ from . import geometry
 from . import ops
 from . import tuning
 from .pointnet_utils import _fold_linear, linear_bn
+from .losses import head_log_softmax
 from .train import linear_bn_train
 
 
@@ -89,7 +90,7 @@ class _FCHead(nn.Module):
             wb = self._folded()
             if wb is not None:
                 return ops.fc_tail(x, wb, True)
-        y = F.log_softmax(self._fc(x), -1)
+        y = head_log_softmax(self._fc(x))  # tuning key train_loss
         return y, y.data.max(1)[1]
 
     def _make_fc(self, out):

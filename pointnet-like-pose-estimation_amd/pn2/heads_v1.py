@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from . import tuning
 from .pointnet2_utils import _needs_autograd
+from .losses import head_log_softmax
 from .train import linear_bn_train
 from .pointnet_utils import (PointNetEncoder, TNet3d, TNetkd, _rows_to_cf, linear_bn, mlp_mode,
                              run_mlp)
@@ -122,7 +123,7 @@ class PointNetCls(nn.Module):
             x = F.relu(self.bn1(self.fc1(x)))
             x = F.relu(self.bn2(self.dropout(self.fc2(x))))
             x = self.fc3(x)
-        x = F.log_softmax(x, dim=1)
+        x = head_log_softmax(x)  # tuning key train_loss
         return x, trans_feat, x.data.max(1)[1]
 
 
@@ -231,7 +232,7 @@ class PoseV1(_ConvStack):
             mean = self.fc2(F.relu(self.bn1(self.fc1(mean))))
             return mean + x
         if self.classify:
-            x = F.log_softmax(x, dim=1)
+            x = head_log_softmax(x)  # tuning key train_loss
             pred_choice = x.data.max(1)[1]
             return x, (-1) ** pred_choice, pred_choice
         return x

@@ -23,6 +23,11 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
   bn_train_forward_direct / bn_relu_apply_direct / group_max_direct / bn_relu_backward_direct
                       (no dispatcher op) train-mode BatchNorm2d + ReLU + torch.max :169-172 and
                       their backward on channels-last rows, around the GEMMs above
+  log_softmax_rows_direct / criterion_forward_direct / criterion_backward_direct /
+  meter_update_direct (no dispatcher op) F.log_softmax and the get_loss classes under autograd
+                      (model/pointnet2_cls_ssg.py:36, 40-47, rotation_ssg.py:40-50,
+                      sign_ssg.py:38-45) and the test loops' per-class bookkeeping
+                      (train_rotation.py:157-163), every sum in a fixed order
   pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
                       channels-last rows (the recompute of pn2.train's frozen mode)
 """
@@ -647,6 +652,120 @@ def fc_rows_backward_direct(dA, Y, x, stats, gamma, beta, relu, frozen):
     """fc_bn_backward_direct for any number of rows (pn2_fc_bn_backward_rows_f32; recorded as
     pn2_fc_rows_backward_f32)."""
     return fc_bn_backward_direct(dA, Y, x, stats, gamma, beta, relu, frozen, rows=True)
+
+
+# ------------------------------------------------------------------------------ losses, metrics
+LOSS_KINDS = {"nll": _lib.LOSS_NLL, "mse": _lib.LOSS_MSE, "l1": _lib.LOSS_L1, "bce": _lib.LOSS_BCE}
+REDUCTIONS = {"mean": _lib.REDUCE_MEAN, "sum": _lib.REDUCE_SUM}
+METER_KINDS = {"cls": _lib.METER_CLS, "sign": _lib.METER_SIGN, "pose": _lib.METER_POSE}
+LOG_SOFTMAX_MAX_K = 1024
+
+
+def log_softmax_rows_direct(x: Tensor) -> Tensor:
+    """x [B,K] -> log_softmax(x, -1) (pn2_log_softmax_rows_f32: per row the float64 sum of
+    exponentials in ascending column order; rows independent of each other and of B)."""
+    x, ldx = _matrix(x, "pn2::log_softmax_rows")
+    B, K = x.shape
+    y = torch.empty(B, K, dtype=torch.float32, device=x.device)
+    _run("pn2_log_softmax_rows_f32", _L.pn2_log_softmax_rows_f32,
+         (x.data_ptr(), ldx, y.data_ptr(), K, B, K, _stream(x)), x.device, nbytes=8.0 * B * K)
+    return y
+
+
+def log_softmax_rows_backward_direct(dy: Tensor, y: Tensor) -> Tensor:
+    """dy [B,K] and the forward's y -> dx = dy - exp(y) * sum_j dy_j
+    (pn2_log_softmax_rows_backward_f32: the row sum one float64 chain in ascending j)."""
+    dy, ldd = _matrix(dy, "pn2::log_softmax_rows_backward")
+    y, ldy = _matrix(y, "pn2::log_softmax_rows_backward")
+    B, K = y.shape
+    if tuple(dy.shape) != (B, K) or dy.device != y.device:
+        raise ValueError("pn2::log_softmax_rows_backward: dy [B,K], y [B,K] on one device")
+    dx = torch.empty(B, K, dtype=torch.float32, device=y.device)
+    _run("pn2_log_softmax_rows_backward_f32", _L.pn2_log_softmax_rows_backward_f32,
+         (dy.data_ptr(), ldd, y.data_ptr(), ldy, dx.data_ptr(), K, B, K, _stream(y)), y.device,
+         nbytes=12.0 * B * K)
+    return dx
+
+
+def _criterion_target(what: str, kind: str, pred: Tensor, target: Tensor) -> Tuple[Tensor, int]:
+    B, K = pred.shape
+    if target.device != pred.device:
+        raise ValueError("%s: pred and target on one device" % what)
+    if kind == "nll":
+        if target.dtype != torch.int64 or tuple(target.shape) != (B,):
+            raise ValueError("%s: nll target int64 [B]" % what)
+        return target.contiguous(), 1
+    if target.dtype != torch.float32 or tuple(target.shape) != (B, K):
+        raise ValueError("%s: target float32 [B,K], pred's shape" % what)
+    return _matrix(target, what)
+
+
+def criterion_forward_direct(kind: str, reduction: str, pred: Tensor, target: Tensor) -> Tensor:
+    """pred [B,K] float32, target (int64 [B] for "nll", float32 [B,K] for "mse" / "l1" / "bce")
+    -> the 0-dim float32 loss with reduction "mean" or "sum" (pn2_criterion_forward_f32: ONE
+    float64 chain over the element terms in row-major order, rounded once)."""
+    what = "pn2::criterion_forward"
+    pred, ldp = _matrix(pred, what)
+    target, ldt = _criterion_target(what, kind, pred, target)
+    B, K = pred.shape
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    _run("pn2_criterion_forward_f32", _L.pn2_criterion_forward_f32,
+         (LOSS_KINDS[kind], REDUCTIONS[reduction], pred.data_ptr(), ldp, target.data_ptr(), ldt, B, K,
+          loss.data_ptr(), _stream(pred)), pred.device, nbytes=8.0 * B * K)
+    return loss
+
+
+def criterion_backward_direct(kind: str, reduction: str, pred: Tensor, target: Tensor, g: Tensor) -> Tensor:
+    """The gradient of criterion_forward_direct with respect to pred for the upstream scalar g
+    (a device tensor of one float32: no host read) -> [B,K] (pn2_criterion_backward_f32)."""
+    what = "pn2::criterion_backward"
+    pred, ldp = _matrix(pred, what)
+    target, ldt = _criterion_target(what, kind, pred, target)
+    if g.dtype != torch.float32 or g.numel() != 1 or g.device != pred.device:
+        raise ValueError("%s: g is one float32 on pred's device" % what)
+    g = g.contiguous()
+    B, K = pred.shape
+    dP = torch.empty(B, K, dtype=torch.float32, device=pred.device)
+    _run("pn2_criterion_backward_f32", _L.pn2_criterion_backward_f32,
+         (LOSS_KINDS[kind], REDUCTIONS[reduction], pred.data_ptr(), ldp, target.data_ptr(), ldt, g.data_ptr(),
+          B, K, dP.data_ptr(), K, _stream(pred)), pred.device, nbytes=12.0 * B * K)
+    return dP
+
+
+def meter_update_direct(kind: str, pred: Tensor, target: Tensor, label: Optional[Tensor], num_category: int,
+                        acc: Tensor, invalid: Tensor, records: Tensor, slot: int) -> None:
+    """One batch into a meter's device state (pn2_meter_update; include/pn2.h has the rules):
+    acc float64 [num_category, W], invalid float64 [1], records float64 [slots, RW], all
+    contiguous.  "cls": pred, target int64 [B]; "sign": pred, target float32 [B] or [B,1], label
+    int64 [B]; "pose": pred, target float32 [B,D], label int64 [B].  No host sync."""
+    what = "pn2::meter_update"
+    dev = pred.device
+    _dev(pred, what)
+    D = pred.shape[1] if kind == "pose" else 1
+    W, RW = (1 + D, D) if kind == "pose" else (2, 1)
+    for t, shape in ((acc, (num_category, W)), (invalid, (1,)), (records, (records.shape[0], RW))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: state is contiguous float64 %s on pred's device" % (what, shape))
+    B = pred.shape[0]
+    if kind == "cls":
+        if pred.dtype != torch.int64 or target.dtype != torch.int64 or tuple(pred.shape) != (B,) or \
+                tuple(target.shape) != (B,) or target.device != dev:
+            raise ValueError("%s: cls takes pred, target int64 [B] on one device" % what)
+        pred, target, ldp, ldt, lp = pred.contiguous(), target.contiguous(), 1, 1, 0
+    else:
+        if kind == "sign":
+            pred, target = pred.reshape(B, 1), target.reshape(B, 1)
+        pred, ldp = _matrix(pred, what)
+        target, ldt = _matrix(target, what)
+        if tuple(target.shape) != (B, D) or target.device != dev:
+            raise ValueError("%s: target has pred's shape and device" % what)
+        if label.dtype != torch.int64 or tuple(label.shape) != (B,) or label.device != dev:
+            raise ValueError("%s: label int64 [B] on pred's device" % what)
+        label = label.contiguous()
+        lp = label.data_ptr()
+    _run("pn2_meter_update", _L.pn2_meter_update,
+         (METER_KINDS[kind], pred.data_ptr(), ldp, target.data_ptr(), ldt, lp, B, D, num_category,
+          acc.data_ptr(), invalid.data_ptr(), records.data_ptr(), slot, records.shape[0], _stream(pred)), dev)
 
 
 # ------------------------------------------------------------------------------ pack_layer

@@ -64,6 +64,23 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      batch (DESIGN.md §4.4 has the measurements).  Batches of 64 rows or fewer
                      run the 64-row kernels either way; with train_head=0 the key does nothing.
                      0 or 1; anything else is an error
+    train_loss       0: the classifiers' log_softmax under autograd (heads._fc_log_softmax, the
+                     two heads_v1 classifiers) is F.log_softmax, a row reduction forward and
+                     backward whose order is torch's choice; 1: pn2.losses.log_softmax
+                     (pn2_log_softmax_rows_f32 / _backward_f32: each row's sums one float64
+                     chain in ascending column order, include/pn2.h).  With the four keys above
+                     at 1 and the criterion from pn2.losses (ClsLoss / PoseLoss / SignLoss: the
+                     loss ONE float64 chain over the element terms in row-major order), a
+                     PointNet++ head's whole train step then has no reduction whose order this
+                     project does not fix; what stays torch is dropout's mask, the optimizer,
+                     sigmoid and the elementwise adds.  The criteria and the meters of
+                     pn2.metrics are the caller's to use and need no key.  The no-autograd eval
+                     path (pn2_fc_tail_f32) is untouched.  Measured (profiles/loss/timing.json,
+                     torch / kernels, forward + backward at B=32): log_softmax 0.027 / 0.051 ms,
+                     nll_loss 0.036 / 0.058 ms, MSELoss(sum) 0.043 / 0.060 ms -- host-bound, the
+                     kernels' route the slower one; the whole ClsSSG B=32 train step 5.746 /
+                     5.746 ms.  The key buys the fixed order, not speed.
+                     0 or 1; anything else is an error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -95,9 +112,11 @@ HOST_DEFAULTS = {
     "train_gemm": 0,
     "train_head": 0,
     "train_head_rows": 0,
+    "train_loss": 0,
 }
 # host keys with a checked range (inclusive); the others take any integer
-HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1), "train_head_rows": (0, 1)}
+HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1), "train_head_rows": (0, 1),
+               "train_loss": (0, 1)}
 
 
 def _check_host(key, value):

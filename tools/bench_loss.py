@@ -1,0 +1,194 @@
+"""The loss, log_softmax and metric kernels (csrc/loss.hip) against what they replace, on
+identical inputs.
+
+  criteria  each criterion of pn2.losses and losses.log_softmax, forward + backward, against the
+            torch function the reference calls, at the training scripts' shapes: [B,7]
+            (log_softmax, nll_loss), [B,3] (MSELoss / L1Loss, reduction 'sum': the scripts'
+            default) and [B,1] (BCELoss), B in 24, 32, 128
+  meter     one test batch (B = 24, 7 categories) into each meter of pn2.metrics -- one launch,
+            no host read -- against the reference test loops' per-class bookkeeping restated in
+            tests/metrics_ref.py on the same device tensors (a boolean-mask index and a host
+            read per category present); wall clock per batch over `batches` batches, the final
+            result() / table arithmetic included
+  step      the whole ClsSSG train step at B = 32 clouds of 1024 points (forward, loss,
+            backward, SGD step) with group_backward=1, train_gemm=1, train_head=1,
+            train_head_rows=1 and F.nll_loss, against the same four keys plus train_loss=1 and
+            losses.ClsLoss
+
+The kernels' claims are a fixed summation order and no per-batch host sync; no ratio is required
+of them.  Method, as tools/bench_fc_train.py: HIP events around `reps` back-to-back calls after
+`warmup` calls, the routes interleaved within each of `rounds` rounds, median (min, max) of the
+rounds; meter and step: wall clock, synchronised at the end.  ratio = torch median / kernels
+median (> 1: the kernels are faster).  Needs a ROCm device.  Writes one JSON document (default
+profiles/loss/timing.json) and prints it."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
+                os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
+import cases  # noqa: E402
+import metrics_ref  # noqa: E402
+from bench_fc_train import interleaved, summary  # noqa: E402
+from pn2 import heads as H  # noqa: E402
+from pn2 import losses, metrics, tuning  # noqa: E402
+
+FOUR = {"group_backward": 1, "train_gemm": 1, "train_head": 1, "train_head_rows": 1}
+
+
+def two_routes(torch_fn, kernel_fn, a):
+    ms = interleaved({"torch": ({}, torch_fn), "kernels": ({}, kernel_fn)}, a)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"ms": {k: summary(v) for k, v in ms.items()},
+            "ratio_torch_over_kernels": round(med["torch"] / med["kernels"], 3)}
+
+
+def bench_criteria(B, a):
+    g = torch.Generator().manual_seed(B)
+    logits = (torch.randn(B, 7, generator=g) * 3).cuda().requires_grad_(True)
+    logp = F.log_softmax(logits.detach(), -1).requires_grad_(True)
+    cls = torch.randint(0, 7, (B,), generator=g).cuda()
+    pose, pose_t = torch.randn(B, 3, generator=g).cuda().requires_grad_(True), torch.randn(B, 3, generator=g).cuda()
+    prob = torch.sigmoid(torch.randn(B, 1, generator=g)).cuda().requires_grad_(True)
+    prob_t = (torch.rand(B, 1, generator=g) < 0.5).float().cuda()
+    R = torch.randn(B, 7, generator=g).cuda()
+
+    def fb(fn, x, *rest):
+        def run():
+            x.grad = None
+            fn(x, *rest).backward()
+        return run
+
+    def ls(fn):
+        def run():
+            logits.grad = None
+            fn(logits).backward(R)
+        return run
+
+    return {
+        "B": B,
+        "log_softmax [B,7]": two_routes(ls(lambda x: F.log_softmax(x, -1)), ls(losses.log_softmax), a),
+        "nll_loss [B,7]": two_routes(fb(F.nll_loss, logp, cls), fb(losses.ClsLoss(), logp, cls), a),
+        "MSELoss(sum) [B,3]": two_routes(fb(nn.MSELoss(reduction="sum"), pose, pose_t),
+                                         fb(losses.PoseLoss("L2_loss", "sum"), pose, pose_t), a),
+        "L1Loss(sum) [B,3]": two_routes(fb(nn.L1Loss(reduction="sum"), pose, pose_t),
+                                        fb(losses.PoseLoss("L1_loss", "sum"), pose, pose_t), a),
+        "BCELoss [B,1]": two_routes(fb(nn.BCELoss(), prob, prob_t), fb(losses.SignLoss(), prob, prob_t), a),
+    }
+
+
+def bench_meter(a):
+    B = 24
+    batch = {k: v.cuda() for k, v in metrics_ref.batches(B, 9)[0].items()}
+    data = [batch] * a.batches
+    loops = {"cls": metrics_ref.classification_test, "sign": metrics_ref.sign_test, "pose": metrics_ref.pose_test}
+    meters = {"cls": metrics.ClassificationMeter, "sign": metrics.SignMeter, "pose": metrics.PoseMeter}
+
+    def feed(kind):
+        m = meters[kind](metrics_ref.NUM_CATEGORY)
+        for d in data:
+            if kind == "cls":
+                m.update(d["pred_choice"], d["label"])
+            elif kind == "sign":
+                m.update(d["sign"], d["sign_target"], d["label"])
+            else:
+                m.update(d["pred"], d["target"], d["label"])
+        return m.result()
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.batches * 1e3
+
+    out = {"B": B, "num_category": metrics_ref.NUM_CATEGORY, "batches": a.batches,
+           "categories_present": int(batch["label"].unique().numel())}
+    for kind in ("cls", "sign", "pose"):
+        routes = {"reference_loop": lambda k=kind: loops[k](data), "meter": lambda k=kind: feed(k)}
+        for fn in routes.values():
+            fn()
+        ms = {k: [] for k in routes}
+        for _ in range(a.rounds):
+            for k, fn in routes.items():
+                ms[k].append(wall(fn))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        out[kind] = {"ms_per_batch": {k: summary(v) for k, v in ms.items()},
+                     "ratio_loop_over_meter": round(med["reference_loop"] / med["meter"], 3)}
+    return out
+
+
+def bench_step(B, a):
+    x = cases.cloud("uniform3", B, 1024, 5).permute(0, 2, 1).contiguous().cuda()
+    y = (torch.arange(B) % 7).cuda()
+    torch.manual_seed(0)
+    model = H.ClsSSG().cuda().train()
+    opt = torch.optim.SGD(model.parameters(), lr=1e-3, momentum=0.9)
+    crit = losses.ClsLoss()
+
+    def step(loss_fn):
+        opt.zero_grad(set_to_none=True)
+        logp, _, _ = model(x)
+        loss_fn(logp, y).backward()
+        opt.step()
+
+    def run(keys, loss_fn):
+        with tuning.override(**keys):
+            for _ in range(3):
+                step(loss_fn)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                step(loss_fn)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / 20 * 1e3
+
+    routes = {"torch_loss": (FOUR, F.nll_loss), "train_loss=1+ClsLoss": (dict(FOUR, train_loss=1), crit)}
+    ms = {k: [] for k in routes}
+    for _ in range(a.rounds):
+        for k, (keys, fn) in routes.items():
+            ms[k].append(run(keys, fn))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"model": "ClsSSG", "B": B, "N": 1024,
+            "keys": "group_backward=1,train_gemm=1,train_head=1,train_head_rows=1",
+            "ms_per_step": {k: summary(v) for k, v in ms.items()},
+            "ratio_torch_over_kernels": round(med["torch_loss"] / med["train_loss=1+ClsLoss"], 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batches", type=int, default=50)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss", "timing.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_loss: needs a ROCm device")
+    doc = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "rounds": a.rounds, "warmup": a.warmup,
+           "protocol": "criteria: HIP events around `reps` back-to-back forward + backward calls per route "
+                       "(identical inputs), after `warmup` calls; routes interleaved within each of `rounds` "
+                       "rounds; median (min, max) of the rounds.  meter: wall clock per batch over `batches` "
+                       "batches fed one after the other, the final readback included, synchronised before and "
+                       "after.  step: wall clock over 20 synchronised train steps after 3.  Routes "
+                       "interleaved; ratio = torch median / kernels median",
+           "criteria": {"B=%d" % B: bench_criteria(B, a) for B in (24, 32, 128)},
+           "meter": bench_meter(a),
+           "step": bench_step(32, a)}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    text = json.dumps(doc, indent=1) + "\n"
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
