@@ -406,7 +406,8 @@ int pn2_fc_bn_backward_f32(const float *dA, int64_t ldd, const float *Y, int64_t
                            float *dY, int64_t ldyy, float *dW, int64_t ldw, float *dbias,
                            float *dgamma, float *dbeta, int flags, void *stream);
 
-/* ---- the same layer for any number of rows (csrc/fc_train.hip, the slab kernels):
+/* ---- the same layer for any number of rows (csrc/fc_train.hip: the entries above are the
+ * one-slab instantiation of its forward / backward kernel template, these the slab loop):
  * pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 take the argument lists of
  * pn2_fc_bn_forward_f32 / pn2_fc_bn_backward_f32, name for name, and serve 1 <= B <= 2^30.
  * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
@@ -423,7 +424,8 @@ int pn2_fc_bn_backward_f32(const float *dA, int64_t ldd, const float *Y, int64_t
  *      accumulators from slab to slab in row order -- so the launch has ceil(N/4) workgroups
  *      whatever B is, and its time grows with B;
  *   3., 4. no float atomics, no wait for another workgroup, no workspace.
- * For B <= pn2_fc_train_max_rows() the results are bit for bit those of the entries above.
+ * For B <= pn2_fc_train_max_rows() the results are bit for bit those of the entries above (one
+ * source for both: every expression and every order of summation is written once).
  * With batch statistics the forward reads its own Y back to write A: Y and A must not overlap
  * (as above).  PN2_EUNSUPPORTED for B > 2^30 (the kernels count rows in an int32). */
 int pn2_fc_bn_forward_rows_f32(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias,

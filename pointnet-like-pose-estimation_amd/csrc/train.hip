@@ -35,6 +35,7 @@
 // of 4 and the bases 16-byte aligned (every SA / v1 layer; the host checks).  The 4-byte sweeps
 // reached 2.9 (partial) and 3.9 TB/s (apply) at SSG training sizes.
 #include "pn2_internal.h"
+#include "bn_elem.h"  // xhat, the activation, dXn: shared with fc_train.hip
 
 namespace pn2 {
 
@@ -44,15 +45,6 @@ constexpr int kTrChunk = 1024;  // rows per chunk (partials per chunk), at most
 constexpr int kTrChunkMin = 64;
 constexpr int kTrMinBlocks = 2048;  // column sweeps: enough blocks to fill 256 CUs several times
 constexpr int kTrUnroll = 8;    // rows in flight per thread in the column sweeps (W = 4: 4)
-
-__device__ __forceinline__ float tr_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
-// xhat for the dgamma sum.  The float32 one is off by up to 2 ulp per row, which the sum over M
-// rows does not average below S2's own size: S2 is a sum of signed terms, about sqrt(M) of them
-// in magnitude, so S2/M in dY lost digits on columns where it came out small (caught by
-// tests/test_gpu_train_kernels.py at C = 2048, M = 8197: 7x the float32 bound of dY).
-__device__ __forceinline__ double tr_xhat64(float y, float mean, float invstd) {
-    return ((double)y - (double)mean) * (double)invstd;
-}
 
 // W adjacent elements of a row: one 16-byte load for W = 4, through vector type V4.  The max
 // kernels pass HIP's float4: with the compiler's own vector type the fused narrow one allocates
@@ -188,14 +180,8 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restr
     const int64_t r1 = r0 + kTrEwRows < M ? r0 + kTrEwRows : M;
 #pragma unroll 4
     for (int64_t r = r0 + ty; r < r1; r += kTrLanes) {
-        const float x = tr_xhat(Y[r * ld + c], mu, is) * ga + be;
-        A[r * lda + c] = relu ? (x > 0.f ? x : 0.f) : x;  // relu is uniform: no divergence
+        A[r * lda + c] = bn_act(Y[r * ld + c], mu, is, ga, be, relu);
     }
-}
-
-// dXn of one element (see header): the incoming gradient d behind the ReLU's mask
-__device__ __forceinline__ float tr_dxn(float xhat, float gamma, float beta, float d, int relu) {
-    return !relu || xhat * gamma + beta > 0.f ? d : 0.f;
 }
 
 // one row's terms of S1 and S2
@@ -205,9 +191,9 @@ __device__ __forceinline__ void tr_bwd_sums(const float (&y)[W], const float (&d
                                             int relu, double (&s)[2][W]) {
 #pragma unroll
     for (int j = 0; j < W; ++j) {
-        const float dd = tr_dxn(tr_xhat(y[j], mu[j], is[j]), ga[j], be[j], d[j], relu);
+        const float dd = bn_dxn(bn_xhat(y[j], mu[j], is[j]), ga[j], be[j], d[j], relu);
         s[0][j] += (double)dd;
-        s[1][j] += (double)dd * tr_xhat64(y[j], mu[j], is[j]);
+        s[1][j] += (double)dd * bn_xhat64(y[j], mu[j], is[j]);
     }
 }
 
@@ -352,8 +338,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
             float o[W];
 #pragma unroll
             for (int j = 0; j < W; ++j) {
-                const float xh = tr_xhat(y[u][j], mu[j], is[j]);
-                const float dd = tr_dxn(xh, ga[j], be[j], d[u][j], relu);
+                const float xh = bn_xhat(y[u][j], mu[j], is[j]);
+                const float dd = bn_dxn(xh, ga[j], be[j], d[u][j], relu);
                 if constexpr (FROZEN)
                     o[j] = ga[j] * is[j] * dd;
                 else
@@ -399,8 +385,7 @@ __device__ __forceinline__ void tr_take(float v, int32_t i, float &m, int32_t &a
 template <bool ACT>
 __device__ __forceinline__ float tr_act(float y, float mu, float is, float ga, float be, int relu) {
     if constexpr (!ACT) return y;
-    const float x = tr_xhat(y, mu, is) * ga + be;
-    return relu ? (x > 0.f ? x : 0.f) : x;
+    return bn_act(y, mu, is, ga, be, relu);
 }
 
 // the per-column BatchNorm constants of a thread's W columns (ACT only: the pointers are null

@@ -558,6 +558,15 @@ def fc_train_max_rows() -> int:
     return int(_L.pn2_fc_train_max_rows())
 
 
+def _fc_entry(direction: str, B: int, rows: Optional[bool]):
+    """(timer name, C entry, error prefix) of the FC forward / backward for B rows: the 64-row
+    entry up to fc_train_max_rows() rows, the any-B entry above; rows forces one of the two."""
+    if B > fc_train_max_rows() if rows is None else rows:
+        return ("pn2_fc_rows_%s_f32" % direction, getattr(_L, "pn2_fc_bn_%s_rows_f32" % direction),
+                "pn2::fc_rows_" + direction)
+    return "pn2_fc_bn_%s_f32" % direction, getattr(_L, "pn2_fc_bn_%s_f32" % direction), "pn2::fc_bn_" + direction
+
+
 def _vector(t: Optional[Tensor], n: int, what: str, like: Tensor) -> int:
     if t is None:
         return 0
@@ -569,14 +578,16 @@ def _vector(t: Optional[Tensor], n: int, what: str, like: Tensor) -> int:
 def fc_bn_forward_direct(x: Tensor, weight: Tensor, bias: Tensor, gamma: Optional[Tensor],
                          beta: Optional[Tensor], running_mean: Optional[Tensor],
                          running_var: Optional[Tensor], eps: float, momentum: float, relu: bool,
-                         frozen: bool, rows: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+                         frozen: bool, rows: Optional[bool] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
     """x [B,K], weight [N,K], bias [N] -> (Y = x W^T + b, A = act(bn(Y)), stats [mean | invstd]
-    or None without BN), one launch (pn2_fc_bn_forward_f32; include/pn2.h states the order
-    rules).  gamma None: no BatchNorm.  frozen: the running statistics normalise and are only
-    read; else batch statistics, and momentum > 0 updates running_mean / running_var in place.
-    Strided 2-D views with unit column stride are read in place.  rows: the any-B entry
-    (fc_rows_forward_direct)."""
-    what = "pn2::fc_rows_forward" if rows else "pn2::fc_bn_forward"
+    or None without BN), one launch: pn2_fc_bn_forward_f32 up to fc_train_max_rows() rows,
+    pn2_fc_bn_forward_rows_f32 (recorded by ops.kernel_timer as pn2_fc_rows_forward_f32) above --
+    the same sums in the same orders (include/pn2.h states the order rules).  gamma None: no
+    BatchNorm.  frozen: the running statistics normalise and are only read; else batch
+    statistics, and momentum > 0 updates running_mean / running_var in place.  Strided 2-D views
+    with unit column stride are read in place.  rows: True / False force the any-B / the 64-row
+    entry whatever B is."""
+    name, entry, what = _fc_entry("forward", x.shape[0] if x.dim() == 2 else 0, rows)
     x, ldx = _matrix(x, what)
     weight, ldw = _matrix(weight, what)
     B, K = x.shape
@@ -592,8 +603,7 @@ def fc_bn_forward_direct(x: Tensor, weight: Tensor, bias: Tensor, gamma: Optiona
     A = torch.empty(B, N, dtype=torch.float32, device=x.device)
     stats = torch.empty(2 * N, dtype=torch.float32, device=x.device) if gamma is not None else None
     flags = (0 if relu else _lib.LAYER_NO_RELU) | (_lib.LAYER_FROZEN_STATS if frozen and gamma is not None else 0)
-    _run(*(("pn2_fc_rows_forward_f32", _L.pn2_fc_bn_forward_rows_f32) if rows else
-           ("pn2_fc_bn_forward_f32", _L.pn2_fc_bn_forward_f32)),
+    _run(name, entry,
          (x.data_ptr(), ldx, weight.data_ptr(), ldw, _vector(bias, N, what, x), B, N, K, float(eps),
           float(momentum) if upd else 0.0,
           _vector(running_mean if use_running else None, N, what, x),
@@ -606,12 +616,13 @@ def fc_bn_forward_direct(x: Tensor, weight: Tensor, bias: Tensor, gamma: Optiona
 
 def fc_bn_backward_direct(dA: Tensor, Y: Tensor, x: Tensor, stats: Optional[Tensor],
                           gamma: Optional[Tensor], beta: Optional[Tensor], relu: bool, frozen: bool,
-                          rows: bool = False):
+                          rows: Optional[bool] = None):
     """The backward of fc_bn_forward_direct up to the layer's own gradients
-    (pn2_fc_bn_backward_f32) -> (dY [B,N], dW [N,K], dbias [N], dgamma, dbeta -- None without
-    BN).  The input gradient is gemm_nn_direct(dY, weight).  rows: the any-B entry
-    (fc_rows_backward_direct)."""
-    what = "pn2::fc_rows_backward" if rows else "pn2::fc_bn_backward"
+    (pn2_fc_bn_backward_f32, or pn2_fc_bn_backward_rows_f32 -- recorded as
+    pn2_fc_rows_backward_f32 -- above fc_train_max_rows() rows; rows as there) -> (dY [B,N],
+    dW [N,K], dbias [N], dgamma, dbeta -- None without BN).  The input gradient is
+    gemm_nn_direct(dY, weight)."""
+    name, entry, what = _fc_entry("backward", Y.shape[0] if Y.dim() == 2 else 0, rows)
     dA, ldd = _matrix(dA, what)
     Y, ldy = _matrix(Y, what)
     x, ldx = _matrix(x, what)
@@ -629,8 +640,7 @@ def fc_bn_backward_direct(dA: Tensor, Y: Tensor, x: Tensor, stats: Optional[Tens
     dgamma = torch.empty(N, dtype=torch.float32, device=x.device) if bn else None
     dbeta = torch.empty(N, dtype=torch.float32, device=x.device) if bn else None
     flags = (0 if relu else _lib.LAYER_NO_RELU) | (_lib.LAYER_FROZEN_STATS if frozen and bn else 0)
-    _run(*(("pn2_fc_rows_backward_f32", _L.pn2_fc_bn_backward_rows_f32) if rows else
-           ("pn2_fc_bn_backward_f32", _L.pn2_fc_bn_backward_f32)),
+    _run(name, entry,
          (dA.data_ptr(), ldd, Y.data_ptr(), ldy, x.data_ptr(), ldx, stats.data_ptr() if bn else 0,
           _vector(gamma, N, what, x), _vector(beta if bn else None, N, what, x), B, N, K,
           dY.data_ptr(), N, dW.data_ptr(), K, dbias.data_ptr(), dgamma.data_ptr() if bn else 0,
@@ -641,16 +651,14 @@ def fc_bn_backward_direct(dA: Tensor, Y: Tensor, x: Tensor, stats: Optional[Tens
 
 def fc_rows_forward_direct(x, weight, bias, gamma, beta, running_mean, running_var, eps, momentum, relu,
                            frozen):
-    """fc_bn_forward_direct for any number of rows: pn2_fc_bn_forward_rows_f32, the same sums in
-    the same orders with the rows walked in slabs (the same bits up to fc_train_max_rows()
-    rows); ops.kernel_timer records it as pn2_fc_rows_forward_f32."""
+    """fc_bn_forward_direct on the any-B entry whatever B is (the same bits up to
+    fc_train_max_rows() rows)."""
     return fc_bn_forward_direct(x, weight, bias, gamma, beta, running_mean, running_var, eps, momentum, relu,
                                 frozen, rows=True)
 
 
 def fc_rows_backward_direct(dA, Y, x, stats, gamma, beta, relu, frozen):
-    """fc_bn_backward_direct for any number of rows (pn2_fc_bn_backward_rows_f32; recorded as
-    pn2_fc_rows_backward_f32)."""
+    """fc_bn_backward_direct on the any-B entry whatever B is."""
     return fc_bn_backward_direct(dA, Y, x, stats, gamma, beta, relu, frozen, rows=True)
 
 

@@ -40,7 +40,7 @@ the FC tails, the translation heads' mean MLP and the T-Nets' tail under autogra
 (batch statistics) and in eval mode (frozen), one launch forward and one backward
 (csrc/fc_train.hip: the whole batch inside one workgroup, float64 column sums in row order),
 plus pn2_gemm_nn_f32 for the input gradient.  Batches above pn2_fc_train_max_rows() (64) rows
-keep the modules, or with tuning key train_head_rows=1 run the same file's slab kernels
+keep the modules, or with tuning key train_head_rows=1 run the same kernel pair's slab loop
 (pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32): the same sums in the same orders.
 """
 import torch
@@ -298,18 +298,16 @@ def point_mlp_train(x, convs, bns, rows, pool=True, last_relu=True):
 class _FcBnTrain(torch.autograd.Function):
     """One FC layer of a head under autograd: Linear (+ BatchNorm1d with batch or frozen
     statistics) (+ ReLU) as pn2_fc_bn_forward_f32, its backward as pn2_fc_bn_backward_f32 plus
-    pn2_gemm_nn_f32 for the input gradient -- every sum in a fixed order (include/pn2.h).  A
-    batch above ops.fc_train_max_rows() rows takes the two entries' any-B forms
-    (ops.fc_rows_forward_direct / fc_rows_backward_direct).  Saved for the backward: x, Y, stats and the parameters, nothing else (A is recomputed)."""
+    pn2_gemm_nn_f32 for the input gradient -- every sum in a fixed order (include/pn2.h).  The
+    ops take the two entries' any-B forms above ops.fc_train_max_rows() rows.  Saved for the
+    backward: x, Y, stats and the parameters, nothing else (A is recomputed)."""
 
     @staticmethod
     def forward(ctx, x, cfg, W, b, g, be):
         """cfg = (eps, momentum factor, running_mean, running_var, relu, frozen); g / be None:
         no BatchNorm."""
         eps, mom, rm, rv, relu, frozen = cfg
-        ctx.rows = x.shape[0] > ops.fc_train_max_rows()
-        fwd = ops.fc_rows_forward_direct if ctx.rows else ops.fc_bn_forward_direct
-        Y, A, stats = fwd(x, W, b, g, be, rm, rv, eps, mom, relu, frozen)
+        Y, A, stats = ops.fc_bn_forward_direct(x, W, b, g, be, rm, rv, eps, mom, relu, frozen)
         ctx.relu, ctx.frozen, ctx.bn = relu, frozen, g is not None
         if ctx.bn:
             ctx.save_for_backward(x, Y, W, stats, g, be)
@@ -323,8 +321,7 @@ class _FcBnTrain(torch.autograd.Function):
             x, Y, W, stats, g, be = ctx.saved_tensors
         else:
             (x, Y, W), stats, g, be = ctx.saved_tensors, None, None, None
-        bwd = ops.fc_rows_backward_direct if ctx.rows else ops.fc_bn_backward_direct
-        dY, dW, db, dg, dbe = bwd(dA, Y, x, stats, g, be, ctx.relu, ctx.frozen)
+        dY, dW, db, dg, dbe = ops.fc_bn_backward_direct(dA, Y, x, stats, g, be, ctx.relu, ctx.frozen)
         dx = ops.gemm_nn_direct(dY, W) if ctx.needs_input_grad[0] else None
         return dx, None, dW, db, dg, dbe
 
@@ -334,10 +331,10 @@ def linear_bn_train(x, fc, bn, relu=True):
     reference's tails (pointnet2_cls_ssg.py:32-35), ``fc(x)`` alone with bn=None, relu=False --
     on the kernels of csrc/fc_train.hip.  The BN mode is the module's: training = batch
     statistics (running statistics and num_batches_tracked updated as torch does), eval =
-    frozen running statistics.  Up to pn2_fc_train_max_rows() (64) rows run the 64-row kernels;
-    more rows run the slab kernels (pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32,
-    the same sums in the same orders) when the tuning keys train_head and train_head_rows are
-    both 1, and fall back to the modules otherwise.  Falls back to the modules as well for what
+    frozen running statistics.  Up to pn2_fc_train_max_rows() (64) rows run the kernel pair's
+    one-slab instantiation; more rows run its slab loop (pn2_fc_bn_forward_rows_f32 /
+    pn2_fc_bn_backward_rows_f32, the same sums in the same orders) when the tuning keys
+    train_head and train_head_rows are both 1, and fall back to the modules otherwise.  Falls back to the modules as well for what
     no kernel covers: non-float32 or host tensors, a Linear without bias, a non-affine BN, an
     eval-mode BN without running statistics; and for a train-mode BN on a single row, where the
     modules raise their ValueError."""

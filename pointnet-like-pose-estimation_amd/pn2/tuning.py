@@ -58,11 +58,12 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      pn2_fc_train_max_rows() (64) rows stays the torch modules, so above 64 rows
                      the reproducibility route above does not hold; 1: such a batch runs
                      pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 (+ pn2_gemm_nn_f32),
-                     the same sums in the same fixed orders at any number of rows -- each
-                     column's rows are one serial chain inside one workgroup, so these launches
-                     have no more workgroups than at 64 rows and their time grows with the
-                     batch (DESIGN.md §4.4 has the measurements).  Batches of 64 rows or fewer
-                     run the 64-row kernels either way; with train_head=0 the key does nothing.
+                     the same kernel pair with its slab loop at run-time length: the same sums
+                     in the same fixed orders at any number of rows -- each column's rows are
+                     one serial chain inside one workgroup, so these launches have no more
+                     workgroups than at 64 rows and their time grows with the batch (DESIGN.md
+                     §4.4 has the measurements).  Batches of 64 rows or fewer run the one-slab
+                     instantiation either way; with train_head=0 the key does nothing.
                      0 or 1; anything else is an error
     train_loss       0: the classifiers' log_softmax under autograd (heads._fc_log_softmax, the
                      two heads_v1 classifiers) is F.log_softmax, a row reduction forward and

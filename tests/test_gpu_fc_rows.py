@@ -1,13 +1,19 @@
 """pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32 (csrc/fc_train.hip, the slab
-kernels; contract in include/pn2.h), ops.fc_rows_*_direct and the train_head_rows route of
-train.linear_bn_train.
+instantiation of its kernel pair; contract in include/pn2.h), ops.fc_rows_*_direct and the
+train_head_rows route of train.linear_bn_train.  The entries are driven by test_gpu_fc_train's
+run_entries.
 
 Below the 64-row limit the any-B entries must give the bits of the 64-row entries; above it the
 order rules are checked directly: rows of Y against the 64-row forward on chunks of X, every
 float64 column sum against an explicit ascending host loop over the GPU's own Y / dY, sampled
 dW elements against a host fma chain.  Values are also held against test_gpu_fc_train's float64
-formulation at its tolerances (Y: the float32-sum bound; 1e-4 forward, 1e-3 gradients)."""
+formulation at its tolerances (Y: the float32-sum bound; 1e-4 forward, 1e-3 gradients).  The
+bits of every output of both pairs are pinned by tests/golden/fc_train_bits.json
+(tools/record_fc_train_bits.py)."""
+import json
+import os
 import struct
+import zlib
 
 import numpy as np
 import pytest
@@ -15,59 +21,13 @@ import torch
 import torch.nn.functional as F
 
 import cases
-from test_gpu_fc_train import (BNS, MOM, _cls_tail, _routes_agree, _two_model_steps, dvec, make_inputs,
-                               reference)
-from test_gpu_train_gemm import Mat, bits, want_and_bound
+from test_gpu_fc_train import (BNS, MOM, OUT, SHAPES, _cls_tail, _routes_agree, _two_model_steps, dvec, make_inputs,
+                               max_rows, reference, run_entries)
+from test_gpu_train_gemm import bits, want_and_bound
 from test_train import close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-NO_RELU, FROZEN = 1, 2
-OUT = ("Y", "A", "stats", "rm", "rv", "dY", "dW", "dbias", "dgamma", "dbeta")
-
-
-def _lib():
-    from pn2 import _lib as lib
-    return lib, lib.load()
-
-
-def run(d, bn, relu, mode, rows, momentum=MOM):
-    """Forward and backward C entries (rows: the any-B pair) on Mat operands -> dict of host
-    results; Mat.result() checks the guard bands around every matrix."""
-    lib, L = _lib()
-    fwd = L.pn2_fc_bn_forward_rows_f32 if rows else L.pn2_fc_bn_forward_f32
-    bwd = L.pn2_fc_bn_backward_rows_f32 if rows else L.pn2_fc_bn_backward_f32
-    B, K = d["X"].shape
-    N = d["W"].shape[0]
-    flags = (0 if relu else NO_RELU) | (FROZEN if bn == "frozen" else 0)
-    x, w, dA = Mat(B, K, mode, d["X"]), Mat(N, K, mode, d["W"]), Mat(B, N, mode, d["dA"])
-    y, a, dy, dw = Mat(B, N, mode), Mat(B, N, mode), Mat(B, N, mode), Mat(N, K, mode)
-    bias, gamma, beta, rm, rv = (dvec(d[k]) for k in ("bias", "gamma", "beta", "rm", "rv"))
-    # vectors with a guard element behind their edge
-    stats, dbias, dgamma, dbeta = (torch.full((n + 1,), float("nan"), device=DEV) for n in (2 * N, N, N, N))
-    has = bn != "none"
-    p = lambda t: t.data_ptr() if has else 0
-    st = lib.stream_ptr(x.buf.device)
-    lib.check(fwd(x.ptr, x.ld, w.ptr, w.ld, bias.data_ptr(), B, N, K, d["eps"], momentum, p(rm), p(rv), p(gamma),
-                  p(beta), y.ptr, y.ld, a.ptr, a.ld, p(stats), flags, st), "forward")
-    lib.check(bwd(dA.ptr, dA.ld, y.ptr, y.ld, x.ptr, x.ld, p(stats), p(gamma), p(beta), B, N, K, dy.ptr, dy.ld,
-                  dw.ptr, dw.ld, dbias.data_ptr(), p(dgamma), p(dbeta), flags, st), "backward")
-    out = {"Y": y.result(), "A": a.result(), "dY": dy.result(), "dW": dw.result(), "rm": rm.cpu().numpy(),
-           "rv": rv.cpu().numpy()}
-    for k, t in (("stats", stats), ("dbias", dbias), ("dgamma", dgamma), ("dbeta", dbeta)):
-        h = t.cpu().numpy()
-        assert np.isnan(h[-1]), "%s: a write behind its edge" % k
-        out[k] = h[:-1]
-    for m, k in ((x, "X"), (w, "W"), (dA, "dA")):  # the inputs keep their bits
-        assert np.array_equal(bits(m.result()), bits(d[k])), k
-    for k in ("Y", "A", "dY", "dW", "dbias"):
-        assert not np.isnan(out[k]).any(), "%s: an element was not written" % k
-    if has:
-        for k in ("stats", "dgamma", "dbeta"):
-            assert not np.isnan(out[k]).any(), "%s: an element was not written" % k
-    else:
-        assert all(np.isnan(out[k]).all() for k in ("stats", "dgamma", "dbeta")), "touched without BN"
-    return out
 
 
 def same_bits(a, b, what=""):
@@ -80,13 +40,15 @@ def same_bits(a, b, what=""):
 # batch statistics of one row are PN2_EINVAL in both pairs (test_abi_fc_rows)
 BELOW = [(B, N, K, bn) for B in (1, 2, 33, 64) for N, K in ((5, 3), (7, 256), (512, 1024)) for bn in BNS
          if not (B == 1 and bn == "batch")]
+BELOW += [(33, 5, 1029, bn) for bn in BNS]  # K > 1024: the backward's second pass over dW's columns
 
 
 @pytest.mark.parametrize("B,N,K,bn", BELOW)
 def test_same_bits_as_the_64_row_entries(B, N, K, bn):
     d = make_inputs(B, N, K, seed=B * 11 + N + K)
     for relu in (1, 0):
-        same_bits(run(d, bn, relu, "contig", rows=True), run(d, bn, relu, "contig", rows=False), "relu=%d" % relu)
+        same_bits(run_entries(d, bn, relu, "contig", rows=True), run_entries(d, bn, relu, "contig", rows=False),
+                  "relu=%d" % relu)
 
 
 # ------------------------------------------------------------------------------ row independence
@@ -124,7 +86,7 @@ def fma32(a, b, c):
     return np.float32(t)
 
 
-RULE_CASES = [(65, 1, 1), (65, 5, 3), (65, 7, 259), (129, 1, 6), (129, 5, 259), (129, 7, 3)]
+RULE_CASES = [(65, 1, 1), (65, 5, 3), (65, 7, 259), (129, 1, 6), (129, 5, 259), (129, 7, 3), (65, 5, 1029)]
 
 
 @pytest.mark.parametrize("bn", ["batch", "frozen"])
@@ -133,7 +95,7 @@ def test_column_sums_and_dw_follow_the_rule(B, N, K, bn):
     d = make_inputs(B, N, K, seed=B * 5 + N * 3 + K)
     want = reference(d, bn, 1)
     d["dA"] = want["dA"]  # nothing rides on the side of the ReLU's kink against float64 below
-    got = run(d, bn, 1, "contig", rows=True)
+    got = run_entries(d, bn, 1, "contig", rows=True)
     f64 = np.float64
     Y, dY, eps = got["Y"], got["dY"], d["eps"]
     if bn == "batch":
@@ -217,6 +179,46 @@ def test_fma32_rounds_once():
         assert bits(fma32(a, b, c)) == bits(cand[0]), (a, b, c)
 
 
+# ------------------------------------------------------------------------------ recorded bits
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fc_train_bits.json")
+
+
+def golden_shapes():
+    shapes = [(max_rows() if B == "max" else B, N, K) for B, N, K in SHAPES]
+    shapes += [c[:3] for c in BELOW] + RULE_CASES + [(33, 5, 1029), (65, 5, 1029), (128, 6, 64), (129, 5, 1028)]
+    return sorted(set(shapes))
+
+
+def golden_bits():
+    """{"B,N,K,bn,relu,entry": {output: CRC32 of its raw bytes}} for every recorded case: each
+    shape with every BN mode (one row: not batch) and with and without ReLU, on the 64-row entries
+    (up to 64 rows) and on the any-B entries, contiguous operands, make_inputs(seed B*11 + N + K)."""
+    out = {}
+    for B, N, K in golden_shapes():
+        d = make_inputs(B, N, K, seed=B * 11 + N + K)
+        for bn in BNS:
+            if B == 1 and bn == "batch":
+                continue
+            for relu in (1, 0):
+                for rows in ([False, True] if B <= max_rows() else [True]):
+                    got = run_entries(d, bn, relu, "contig", rows=rows)
+                    key = "%d,%d,%d,%s,%d,%s" % (B, N, K, bn, relu, "rows" if rows else "64")
+                    out[key] = {k: "%08x" % zlib.crc32(np.ascontiguousarray(got[k], np.float32).tobytes())
+                                for k in OUT}
+    return out
+
+
+def test_bits_are_the_recorded_ones():
+    """Every output of both entry pairs has the bits recorded before the kernels became one
+    template pair (above 64 rows there is no second kernel to compare against)."""
+    with open(GOLDEN) as f:
+        want = json.load(f)["crc32"]
+    got = golden_bits()
+    assert got.keys() == want.keys()
+    bad = ["%s %s" % (k, o) for k in want for o in OUT if got[k][o] != want[k][o]]
+    assert not bad, "%d outputs differ, the first: %s" % (len(bad), ", ".join(bad[:8]))
+
+
 # ------------------------------------------------------------------------------ loads and edges
 @pytest.mark.parametrize("bn", BNS)
 @pytest.mark.parametrize("K", [259, 260])
@@ -225,14 +227,14 @@ def test_leading_dimensions_and_unaligned_bases(K, bn):
     the 16-byte loads off: the same bits as the contiguous case (K = 260: that one runs the
     16-byte path; K = 259: dword loads everywhere), nothing written outside any output."""
     d = make_inputs(65, 5, K, seed=K)
-    base = run(d, bn, 1, "contig", rows=True)
+    base = run_entries(d, bn, 1, "contig", rows=True)
     for mode in ("ld", "offset"):
-        same_bits(run(d, bn, 1, mode, rows=True), base, mode)
+        same_bits(run_entries(d, bn, 1, mode, rows=True), base, mode)
 
 
 def test_momentum_zero_keeps_running_statistics():
     d = make_inputs(65, 5, 6, seed=3)
-    got = run(d, "batch", 1, "contig", rows=True, momentum=0.0)
+    got = run_entries(d, "batch", 1, "contig", rows=True, momentum=0.0)
     assert np.array_equal(bits(got["rm"]), bits(d["rm"])) and np.array_equal(bits(got["rv"]), bits(d["rv"]))
 
 

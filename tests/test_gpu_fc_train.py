@@ -96,58 +96,65 @@ def dvec(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(DEV)
 
 
-def run_entries(d, bn, relu, mode, momentum=MOM):
-    """Both C entries on Mat operands -> dict of host results (guards checked)."""
+OUT = ("Y", "A", "stats", "rm", "rv", "dY", "dW", "dbias", "dgamma", "dbeta")
+
+
+def run_entries(d, bn, relu, mode, momentum=MOM, rows=False):
+    """The forward and the backward C entry (rows: the any-B pair) on Mat operands, the upstream
+    gradient d["dA"] -> dict of host results.  Mat.result() checks the guard bands around every
+    matrix, the vectors carry a guard element behind their edge, the inputs must keep their bits
+    and every output element must have been written."""
     lib, L = _lib()
+    fwd = L.pn2_fc_bn_forward_rows_f32 if rows else L.pn2_fc_bn_forward_f32
+    bwd = L.pn2_fc_bn_backward_rows_f32 if rows else L.pn2_fc_bn_backward_f32
     B, K = d["X"].shape
     N = d["W"].shape[0]
     flags = (0 if relu else NO_RELU) | (FROZEN if bn == "frozen" else 0)
-    x, w = Mat(B, K, mode, d["X"]), Mat(N, K, mode, d["W"])
-    y, a = Mat(B, N, mode), Mat(B, N, mode)
+    x, w, dA = Mat(B, K, mode, d["X"]), Mat(N, K, mode, d["W"]), Mat(B, N, mode, d["dA"])
+    y, a, dy, dw = Mat(B, N, mode), Mat(B, N, mode), Mat(B, N, mode), Mat(N, K, mode)
     bias, gamma, beta, rm, rv = (dvec(d[k]) for k in ("bias", "gamma", "beta", "rm", "rv"))
-    stats = torch.full((2 * N,), float("nan"), device=DEV)
+    stats, dbias, dgamma, dbeta = (torch.full((n + 1,), float("nan"), device=DEV) for n in (2 * N, N, N, N))
     has = bn != "none"
     p = lambda t: t.data_ptr() if has else 0
     st = lib.stream_ptr(x.buf.device)
-    lib.check(L.pn2_fc_bn_forward_f32(x.ptr, x.ld, w.ptr, w.ld, bias.data_ptr(), B, N, K, d["eps"], momentum,
-                                      p(rm), p(rv), p(gamma), p(beta), y.ptr, y.ld, a.ptr, a.ld, p(stats),
-                                      flags, st), "pn2_fc_bn_forward_f32")
-    out = {"Y": y.result(), "A": a.result(), "stats": stats.cpu().numpy(), "rm": rm.cpu().numpy(),
-           "rv": rv.cpu().numpy()}
-    dA = Mat(B, N, mode, d["dA_masked"])
-    dy, dw = Mat(B, N, mode), Mat(N, K, mode)
-    dbias, dgamma, dbeta = (torch.full((N,), float("nan"), device=DEV) for _ in range(3))
-    lib.check(L.pn2_fc_bn_backward_f32(dA.ptr, dA.ld, y.ptr, y.ld, x.ptr, x.ld, p(stats), p(gamma), p(beta),
-                                       B, N, K, dy.ptr, dy.ld, dw.ptr, dw.ld, dbias.data_ptr(), p(dgamma),
-                                       p(dbeta), flags, st), "pn2_fc_bn_backward_f32")
-    out.update(dY=dy.result(), dW=dw.result(), dbias=dbias.cpu().numpy(), dgamma=dgamma.cpu().numpy(),
-               dbeta=dbeta.cpu().numpy())
-    # the inputs keep their bits
-    for m, k in ((x, "X"), (w, "W"), (dA, "dA_masked")):
+    lib.check(fwd(x.ptr, x.ld, w.ptr, w.ld, bias.data_ptr(), B, N, K, d["eps"], momentum, p(rm), p(rv), p(gamma),
+                  p(beta), y.ptr, y.ld, a.ptr, a.ld, p(stats), flags, st), "forward")
+    out = {"Y": y.result(), "A": a.result(), "rm": rm.cpu().numpy(), "rv": rv.cpu().numpy()}
+    lib.check(bwd(dA.ptr, dA.ld, y.ptr, y.ld, x.ptr, x.ld, p(stats), p(gamma), p(beta), B, N, K, dy.ptr, dy.ld,
+                  dw.ptr, dw.ld, dbias.data_ptr(), p(dgamma), p(dbeta), flags, st), "backward")
+    out.update(dY=dy.result(), dW=dw.result())
+    for k, t in (("stats", stats), ("dbias", dbias), ("dgamma", dgamma), ("dbeta", dbeta)):
+        h = t.cpu().numpy()
+        assert np.isnan(h[-1]), "%s: a write behind its edge" % k
+        out[k] = h[:-1]
+    # the inputs keep their bits (Y is the backward's input)
+    for m, k in ((x, "X"), (w, "W"), (dA, "dA")):
         assert np.array_equal(bits(m.result()), bits(d[k])), k
-    assert np.array_equal(bits(y.result()), bits(out["Y"]))
+    assert np.array_equal(bits(y.result()), bits(out["Y"])), "Y"
     for t, k in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
         assert np.array_equal(bits(t.cpu().numpy()), bits(d[k])), k
+    for k in ("Y", "A", "dY", "dW", "dbias"):
+        assert not np.isnan(out[k]).any(), "%s: an element was not written" % k
+    if has:
+        for k in ("stats", "dgamma", "dbeta"):
+            assert not np.isnan(out[k]).any(), "%s: an element was not written" % k
+    else:
+        assert all(np.isnan(out[k]).all() for k in ("stats", "dgamma", "dbeta")), "touched without BN"
     return out
 
 
 def check_case(B, N, K, bn, relu, mode, seed, ties=False, momentum=MOM):
     d = make_inputs(B, N, K, seed, ties)
     want = reference(d, bn, relu)
-    d["dA_masked"] = want["dA"]
+    d["dA"] = want["dA"]
     got = run_entries(d, bn, relu, mode, momentum)
-    for k in ("Y", "A", "dY", "dW", "dbias"):
-        assert not np.isnan(got[k]).any(), "%s: an element was not written" % k
     _, bound = want_and_bound("nt", d["X"], d["W"], d["bias"])
     err = np.abs(got["Y"].astype(np.float64) - want["Y"])
     worst = float((err / np.maximum(bound, 1e-300)).max())
     print("B=%d N=%d K=%d %s relu=%d %s: Y worst error / bound = %.3f" % (B, N, K, bn, relu, mode, worst))
     assert (err <= bound).all(), "Y worst error / bound = %.3f" % worst
     close(got["A"], want["A"], 1e-4, "A")
-    if bn == "none":
-        assert np.isnan(got["stats"]).all(), "stats touched without BN"
-        assert np.isnan(got["dgamma"]).all() and np.isnan(got["dbeta"]).all()
-    else:
+    if bn != "none":
         close(got["stats"][:N], want["mean"], 1e-4, "mean")
         close(got["stats"][N:], want["invstd"], 1e-4, "invstd")
         close(got["dgamma"], want["dgamma"], 1e-3, "dgamma")
@@ -218,13 +225,13 @@ def test_row_independence_of_y():
 # ------------------------------------------------------------------------------ order observable
 def test_dbeta_is_the_ascending_float64_sum():
     d = make_inputs(37, 70, 131, seed=5)
-    d["dA_masked"] = reference(d, "batch", 1)["dA"]
+    d["dA"] = reference(d, "batch", 1)["dA"]
     got = run_entries(d, "batch", 1, "contig")
     N = 70
     mu, is_ = got["stats"][:N], got["stats"][N:]
     pre = ((got["Y"] - mu) * is_) * d["gamma"] + d["beta"]  # float32, each operation rounded
     assert pre.dtype == np.float32
-    dXn = np.where(pre > 0, d["dA_masked"], np.float32(0))
+    dXn = np.where(pre > 0, d["dA"], np.float32(0))
     s64 = np.zeros(N, np.float64)
     s32 = np.zeros(N, np.float32)
     for r in range(37):
@@ -237,7 +244,7 @@ def test_dbeta_is_the_ascending_float64_sum():
 @pytest.mark.parametrize("bn", BNS)
 def test_same_bits_twice(bn):
     d = make_inputs(33, 70, 259, seed=41)
-    d["dA_masked"] = reference(d, bn, 1)["dA"]
+    d["dA"] = reference(d, bn, 1)["dA"]
     a = run_entries(d, bn, 1, "ld")
     b = run_entries(d, bn, 1, "ld")
     assert a.keys() == b.keys()

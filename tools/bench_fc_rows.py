@@ -30,8 +30,9 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
                 os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
+import bench_common  # noqa: E402
 import cases  # noqa: E402
-from bench_fc_train import REPRO, interleaved, summary  # noqa: E402
+from bench_common import REPRO, summary  # noqa: E402
 from pn2 import heads as H  # noqa: E402
 from pn2 import ops, tuning  # noqa: E402
 
@@ -40,10 +41,7 @@ KERNELS = {"train_head": 1, "train_head_rows": 1}
 
 
 def two_routes(fn, a):
-    ms = interleaved({"modules": (MODULES, fn), "kernels": (KERNELS, fn)}, a)
-    med = {k: statistics.median(v) for k, v in ms.items()}
-    return {"ms": {k: summary(v) for k, v in ms.items()},
-            "ratio_modules_over_kernels": round(med["modules"] / med["kernels"], 3)}
+    return bench_common.two_routes({"modules": (MODULES, fn), "kernels": (KERNELS, fn)}, a)
 
 
 def launches(fn):

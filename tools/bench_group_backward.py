@@ -32,8 +32,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
-                os.path.join(ROOT, "tests", "golden")]
+                os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
 import cases  # noqa: E402
+from bench_common import summary, timed  # noqa: E402
 from pn2 import heads as H  # noqa: E402
 from pn2 import ops, train, tuning  # noqa: E402
 
@@ -45,20 +46,6 @@ SHAPES = [  # name, K, radius, D, feature_first, adversarial
     ("adversarial", 64, 0.4, 128, False, True),
 ]
 N, S, C = 512, 128, 3
-
-
-def summary(ms):
-    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def bench_shape(B, K, radius, D, ff, adversarial, a):

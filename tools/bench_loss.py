@@ -35,9 +35,10 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
                 os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
+import bench_common  # noqa: E402
 import cases  # noqa: E402
 import metrics_ref  # noqa: E402
-from bench_fc_train import interleaved, summary  # noqa: E402
+from bench_common import summary  # noqa: E402
 from pn2 import heads as H  # noqa: E402
 from pn2 import losses, metrics, tuning  # noqa: E402
 
@@ -45,10 +46,7 @@ FOUR = {"group_backward": 1, "train_gemm": 1, "train_head": 1, "train_head_rows"
 
 
 def two_routes(torch_fn, kernel_fn, a):
-    ms = interleaved({"torch": ({}, torch_fn), "kernels": ({}, kernel_fn)}, a)
-    med = {k: statistics.median(v) for k, v in ms.items()}
-    return {"ms": {k: summary(v) for k, v in ms.items()},
-            "ratio_torch_over_kernels": round(med["torch"] / med["kernels"], 3)}
+    return bench_common.two_routes({"torch": ({}, torch_fn), "kernels": ({}, kernel_fn)}, a)
 
 
 def bench_criteria(B, a):

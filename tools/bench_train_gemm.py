@@ -29,8 +29,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "pointnet-like-pose-estimation_amd"),
-                os.path.join(ROOT, "tests", "golden")]
+                os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
 import cases  # noqa: E402
+from bench_common import summary, timed  # noqa: E402
 from pn2 import heads as H  # noqa: E402
 from pn2 import ops, train, tuning  # noqa: E402
 
@@ -39,20 +40,6 @@ LAYERS = [  # module, rows per cloud, channel chain
     ("sa2", 128 * 64, [131, 128, 128, 256]),
     ("sa3", 128, [259, 256, 512, 1024]),
 ]
-
-
-def summary(ms):
-    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def bench_product(runs, a):
