@@ -211,7 +211,6 @@ __device__ __forceinline__ Split hid_split(const F8 &x, float up = 1.f) {
 __device__ __forceinline__ ActScale wave_act_scale(unsigned lane_max_bits) {
     return act_scale(__uint_as_float(wave_max_u32(lane_max_bits)));
 }
-__device__ __forceinline__ unsigned mag_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 __device__ __forceinline__ unsigned hid_dep(const Split &x) {
     return __builtin_bit_cast(unsigned, __builtin_shufflevector(x.h, x.h, 0, 1));
 }
@@ -280,12 +279,6 @@ __device__ __forceinline__ void stage_wait() {
 // not see that global_load_lds (addressed through M0) writes that buffer, so the memory clobber
 // also keeps those reads from being scheduled after the refill.
 __device__ __forceinline__ void ring_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ void stage_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // KB0M > 0: the layer-0 input (<= KB0M k-blocks) is gathered once into registers and layer 0 runs
 // tile by tile from the ring like layers 1 and 2; KB0M == 0: layer 0 streams its input blocks
@@ -630,7 +623,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int kb = 0; kb < KB0M; ++kb)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) mb = max(mb, mag_bits(x[kb][j]));
+                for (int j = 0; j < 8; ++j) mb = max(mb, abs_bits(x[kb][j]));
             const ActScale sc = wave_act_scale(mb);
 #pragma unroll
             for (int kb = 0; kb < KB0M; ++kb)

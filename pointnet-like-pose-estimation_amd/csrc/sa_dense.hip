@@ -121,7 +121,6 @@ __host__ __device__ __forceinline__ int64_t frag_off(int64_t row, int col, int k
 // producing layer's per-(row block, tile) maxima (in_max, rows mode), or -- a first layer over
 // points (mode 1: group_all, the pre-pass) -- the rows themselves, read once more before the
 // main loop ([xyz | features], L2-resident; lane (r, h) takes every other channel of row r)
-__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
 template <int NP>
 __device__ __forceinline__ ActScale dense_act_scale(const DenseSplitArgs &A, int rb, int lane) {
     if constexpr (NP != 2) {
@@ -196,11 +195,108 @@ __device__ __forceinline__ void dma16(const char *src, char *dst) {
     __builtin_amdgcn_global_load_lds(src, (lds_void *)dst, 16, 0, 0);
 }
 
-// raw s_barrier (__syncthreads' fence would wait vmcnt(0) and drain the DMA ring)
-__device__ __forceinline__ void stage_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+// ------------------------------------------------------------------ pieces the kernels share
+// dense_lds_kernel and dense_pair_kernel must produce dense_split_kernel's bits for the same layer
+// (tests/test_gpu_dense_bits.py holds them): what follows exists once for the kernels that use it.
+
+// Block 0 of a group_all row: raw xyz (sample_and_group_all does not centre) of the point at
+// prow (channel stride pc), zeros past C, in the A-fragment order -- lane half h holds channel
+// (j&3) + 8(j>>2) + 4h in element j
+__device__ __forceinline__ void load_xyz_block(const float *prow, int64_t pc, int C, int h, float (&x)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ch = (j & 3) + 8 * (j >> 2) + 4 * h;
+        x[j] = ch < C ? prow[(int64_t)ch * pc] : 0.f;
+    }
+}
+
+// lane's weight fragment of one (tile, k-block) straight from the image: plane p at wq[p * plane]
+template <int NP>
+__device__ __forceinline__ Split load_wfrag(const bf16x8 *wq, int64_t plane) {
+    Split w;
+    w.h = wq[0];
+    w.m = NP >= 2 ? wq[plane] : w.h;
+    w.l = NP == 3 ? wq[2 * plane] : w.h;
+    return w;
+}
+
+// The zero side job: this workgroup's share of [zrows][zcols] floats at A.zero (the next layer's
+// pool, or the caller's zero_out; stream order publishes it).  GRID2D: the launch's workgroups
+// are gridDim.x * gridDim.y (dense_split_kernel), else gridDim.x.  (The grid is read inside the
+// branch: hoisted to the call as (wg, nwg) arguments, dense_lds_kernel compiled to other
+// register assignments.)
+template <bool GRID2D>
+__device__ __forceinline__ void zero_share(const DenseSplitArgs &A, int tid, int nthreads) {
+    if (A.zero) {
+        const int64_t tot = A.zrows * A.zcols, nwg = GRID2D ? (int64_t)gridDim.x * gridDim.y : gridDim.x;
+        const int64_t per = (tot + nwg - 1) / nwg,
+                      e0 = (int64_t)(GRID2D ? blockIdx.x + blockIdx.y * gridDim.x : blockIdx.x) * per;
+        const int64_t e1 = e0 + per < tot ? e0 + per : tot;
+        for (int64_t e = e0 + tid; e < e1; e += nthreads) {
+            const int64_t g = e / A.zcols;
+            A.zero[g * A.zstride + (e - g * A.zcols)] = 0.f;
+        }
+    }
+}
+
+// one output element: the accumulator as it is (raw; al = the NP = 2 scales or 1), or BN with or
+// without ReLU
+__device__ __forceinline__ float dense_value(const DenseSplitArgs &A, float acc, float al, float be) {
+    const float y = __builtin_fmaf(acc, al, be);
+    return A.raw ? acc * al : (A.norelu ? y : chain_relu(y));
+}
+
+// an unpooled element (row, col): its value, stored in row order or fragment order (frag_out),
+// and folded into tmax, the max |value| written (A.out_max)
+__device__ __forceinline__ void store_value(const DenseSplitArgs &A, int row, int col, float acc, float al, float be, unsigned &tmax) {
+    const float v = dense_value(A, acc, al, be);
+    A.out[A.frag_out ? frag_off(row, col, 2 * A.tiles) : (int64_t)row * A.ostride + col] = v;
+    tmax = max(tmax, __float_as_uint(v) & 0x7FFFFFFFu);
+}
+
+// max over rows of relu(fma(acc, al, be)) = relu(fma(row max (al >= 0) or min, al, be))
+__device__ __forceinline__ float pooled_value(const DenseSplitArgs &A, float mx, float mn, float al, float be) {
+    const float y = __builtin_fmaf(al >= 0.f ? mx : mn, al, be);
+    return A.norelu ? y : chain_relu(y);
+}
+
+// the workgroup's LDS pool ([gpb groups][pcols columns from tile ct0], keys where norelu; the
+// workgroup's rows start at row0) -> the G groups' output rows
+__device__ __forceinline__ void flush_lds_pool(const DenseSplitArgs &A, const unsigned *opool, int gpb, int pcols,
+                                               int row0, int ct0, unsigned G, int tid, int nthreads) {
+    __syncthreads();
+    for (int e = tid; e < gpb * pcols; e += nthreads) {
+        const int gl = e / pcols, c = e - gl * pcols;
+        const unsigned gg = (unsigned)(row0 / A.K + gl);
+        if (gg < G)
+            A.out[(int64_t)gg * A.ostride + 32 * ct0 + c] = A.norelu ? funkey(opool[e]) : __uint_as_float(opool[e]);
+    }
+}
+
+// Pooled epilogue of one 32 x 32 tile whose slab lies in one group (K % 32 == 0): the max of the
+// slab's rows into the workgroup's LDS pool (lds: `opool` [groups of the workgroup][pcols], the
+// workgroup's rows starting at row0, this lane's pool column lcol) or into the zeroed output in
+// HBM
+__device__ __forceinline__ void pool_tile(const DenseSplitArgs &A, int slab_row, int row0, int col, const cfloatx16 &acc,
+                                          float al, float be, int h, bool lds, unsigned *opool, int pcols, int lcol) {
+    float mx = acc[0], mn = acc[0];
+#pragma unroll
+    for (int q = 1; q < 16; ++q) {
+        mx = fmaxf(mx, acc[q]);
+        mn = fminf(mn, acc[q]);
+    }
+    mx = max_halves(mx);
+    mn = min_halves(mn);
+    const float m = pooled_value(A, mx, mn, al, be);
+    // ReLU output >= +0: its bits order as uints; signed (norelu) values go through fkey
+    const unsigned mk = A.norelu ? fkey(m) : __float_as_uint(m);
+    if (h == 0 && slab_row < A.M) {
+        const unsigned gg = (unsigned)slab_row / (unsigned)A.K;
+        if (lds)
+            atomicMax(opool + ((int)gg - row0 / A.K) * pcols + lcol, mk);
+        else
+            atomicMax(reinterpret_cast<unsigned *>(A.out + (int64_t)gg * A.ostride + col), mk);
+    }
 }
 
 template <int NTC, int NP, bool FAST, int NW>
@@ -223,19 +319,11 @@ void dense_split_kernel(const DenseSplitArgs A) {
     const int ct0 = (int)(lid % gridDim.y) * NTC;  // first output tile
     const int ncols = 32 * NTC;
     char *stages = dsm;
-    float *opool = reinterpret_cast<float *>(dsm + 2 * kStage);  // [groups][ncols]
+    unsigned *opool = reinterpret_cast<unsigned *>(dsm + 2 * kStage);  // [groups][ncols]
     const int gpb = A.pool_mode == 1 ? kDRows / A.K : 0;
     if (A.pool_mode == 1)
-        for (int e = tid; e < gpb * ncols; e += 64 * kDW) opool[e] = 0.f;
-    if (A.zero) {  // this workgroup's share of the next layer's pool (stream order publishes it)
-        const int64_t tot = A.zrows * A.zcols, nwg = (int64_t)gridDim.x * gridDim.y;
-        const int64_t per = (tot + nwg - 1) / nwg, e0 = (int64_t)(blockIdx.x + blockIdx.y * gridDim.x) * per;
-        const int64_t e1 = e0 + per < tot ? e0 + per : tot;
-        for (int64_t e = e0 + tid; e < e1; e += 64 * kDW) {
-            const int64_t g = e / A.zcols;
-            A.zero[g * A.zstride + (e - g * A.zcols)] = 0.f;
-        }
-    }
+        for (int e = tid; e < gpb * ncols; e += 64 * kDW) opool[e] = 0u;
+    zero_share<true>(A, tid, 64 * kDW);
 
     // ---- this lane's row (A operand)
     const int R = row0 + 32 * wave + r;
@@ -261,12 +349,8 @@ void dense_split_kernel(const DenseSplitArgs A) {
             for (int j = 0; j < 8; ++j) x[j] = 0.f;
             return;
         }
-        if (A.mode == 1 && kb == 0) {  // raw xyz (sample_and_group_all does not centre)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int ch = (j & 3) + 8 * (j >> 2) + 4 * h;
-                x[j] = ch < A.C ? prow[(int64_t)ch * A.pc] : 0.f;
-            }
+        if (A.mode == 1 && kb == 0) {
+            load_xyz_block(prow, A.pc, A.C, h, x);
             return;
         }
         if (A.mode == 0 && A.frag_in) {
@@ -439,12 +523,7 @@ void dense_split_kernel(const DenseSplitArgs A) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int row = slab_row + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (row < A.M) {
-                    const float y = __builtin_fmaf(acc[i][q], al, be);
-                    const float v = A.raw ? acc[i][q] * al : (A.norelu ? y : chain_relu(y));
-                    A.out[A.frag_out ? frag_off(row, col, 2 * A.tiles) : (int64_t)row * A.ostride + col] = v;
-                    tmax = max(tmax, __float_as_uint(v) & 0x7FFFFFFFu);
-                }
+                if (row < A.M) store_value(A, row, col, acc[i][q], al, be, tmax);
             }
             if (A.out_max) {
                 const unsigned m = wave_max_u32(tmax);
@@ -452,12 +531,7 @@ void dense_split_kernel(const DenseSplitArgs A) {
             }
             continue;
         }
-        // max over rows of relu(fma(acc, al, be)) = relu(fma(row max (al >= 0) or min, al, be))
-        const bool up = al >= 0.f;
-        auto fin = [&](float mx, float mn) {
-            const float y = __builtin_fmaf(up ? mx : mn, al, be);
-            return A.norelu ? y : chain_relu(y);
-        };
+        auto fin = [&](float mx, float mn) { return pooled_value(A, mx, mn, al, be); };
         if (A.pool_mode == 0) {  // K = 8 or 16: rows 8k..8k+7 are registers 4k..4k+3
             float mx[4], mn[4];
 #pragma unroll
@@ -495,33 +569,9 @@ void dense_split_kernel(const DenseSplitArgs A) {
             }
             continue;
         }
-        float mx = acc[i][0], mn = acc[i][0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) {
-            mx = fmaxf(mx, acc[i][q]);
-            mn = fminf(mn, acc[i][q]);
-        }
-        const float m = fin(max_halves(mx), min_halves(mn));
-        // ReLU output >= +0: its bits order as uints; signed (norelu) values go through fkey
-        const unsigned mk = A.norelu ? fkey(m) : __float_as_uint(m);
-        if (h == 0 && slab_row < A.M) {
-            const unsigned gg = (unsigned)slab_row / (unsigned)A.K;
-            if (A.pool_mode == 1)
-                atomicMax(reinterpret_cast<unsigned *>(opool) + ((int)gg - row0 / A.K) * ncols + 32 * i + r, mk);
-            else
-                atomicMax(reinterpret_cast<unsigned *>(A.out + (int64_t)gg * A.ostride + col), mk);
-        }
+        pool_tile(A, slab_row, row0, col, acc[i], al, be, h, A.pool_mode == 1, opool, ncols, 32 * i + r);
     }
-    if (A.pool && A.pool_mode == 1) {
-        __syncthreads();
-        for (int e = tid; e < gpb * ncols; e += 64 * kDW) {
-            const int gl = e / ncols, c = e - gl * ncols;
-            const unsigned gg = (unsigned)(row0 / A.K + gl);
-            if (gg < G)
-                A.out[(int64_t)gg * A.ostride + 32 * ct0 + c] =
-                    A.norelu ? funkey(__float_as_uint(opool[e])) : opool[e];
-        }
-    }
+    if (A.pool && A.pool_mode == 1) flush_lds_pool(A, opool, gpb, ncols, row0, ct0, G, tid, 64 * kDW);
     PN2_DSTAMP(15);
 }
 
@@ -611,15 +661,7 @@ void dense_lds_kernel(const DenseSplitArgs A) {
     }
     const int row0 = (int)rbi * TR;
     const int ct0 = (int)cti * NT;  // first 32-column tile of the workgroup
-    if (A.zero) {  // a side job: the next layer's pool, or the caller's zero_out
-        const int64_t tot = A.zrows * A.zcols, nwg = gridDim.x;
-        const int64_t per = (tot + nwg - 1) / nwg, e0 = (int64_t)blockIdx.x * per;
-        const int64_t e1 = e0 + per < tot ? e0 + per : tot;
-        for (int64_t e = e0 + tid; e < e1; e += 64 * NW) {
-            const int64_t g = e / A.zcols;
-            A.zero[g * A.zstride + (e - g * A.zcols)] = 0.f;
-        }
-    }
+    zero_share<false>(A, tid, 64 * NW);
     const int kb0 = A.mode == 1 ? 1 : 0;        // group_all: block 0 = xyz (registers)
     const int nst = (A.kb - kb0) / 2;           // 32-channel stages
 
@@ -675,27 +717,15 @@ void dense_lds_kernel(const DenseSplitArgs A) {
     const int trow = 32 * wave + r;  // this lane's tile row (A fragment)
     const ActScale asc = dense_act_scale<NP>(A, (row0 >> 5) + wave, lane);
     if (A.mode == 1) {
-        // block 0: raw xyz of the point (sample_and_group_all does not centre), and its
-        // fragments straight from L2
+        // block 0: the point's xyz, and its weight fragments straight from L2
         const int R = min(row0 + trow, A.M - 1);
         const int b = R / A.N, n = R - b * A.N;
-        const float *prow = A.pts + (int64_t)b * A.pb + (int64_t)n * A.pn;
         float x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int ch = (j & 3) + 8 * (j >> 2) + 4 * h;
-            x[j] = ch < A.C ? prow[(int64_t)ch * A.pc] : 0.f;
-        }
+        load_xyz_block(A.pts + (int64_t)b * A.pb + (int64_t)n * A.pn, A.pc, A.C, h, x);
         const Split xs = split_scaled<NP>(x, asc.up);
 #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const bf16x8 *wq = A.w + (int64_t)(ct0 + i) * A.kb * 64 + lane;
-            Split w;
-            w.h = wq[0];
-            w.m = NP >= 2 ? wq[plane] : w.h;
-            w.l = NP == 3 ? wq[2 * plane] : w.h;
-            acc[i] = mma_wb<NP>(xs, w, acc[i]);
-        }
+        for (int i = 0; i < NT; ++i)
+            acc[i] = mma_wb<NP>(xs, load_wfrag<NP>(A.w + (int64_t)(ct0 + i) * A.kb * 64 + lane, plane), acc[i]);
     }
     const int swz = (trow >> 1) & 7;
     constexpr int kLo = kIns / NW, kHi = kLo + (kIns % NW ? 1 : 0);
@@ -817,12 +847,7 @@ void dense_lds_kernel(const DenseSplitArgs A) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int row = slab_row + (q & 3) + 8 * (q >> 2) + 4 * h;
-                if (row < A.M) {
-                    const float y = __builtin_fmaf(acc[i][q], al, be);
-                    const float v = A.raw ? acc[i][q] * al : (A.norelu ? y : chain_relu(y));
-                    A.out[A.frag_out ? frag_off(row, col, 2 * A.tiles) : (int64_t)row * A.ostride + col] = v;
-                    tmax = max(tmax, __float_as_uint(v) & 0x7FFFFFFFu);
-                }
+                if (row < A.M) store_value(A, row, col, acc[i][q], al, be, tmax);
             }
             if (A.out_max) {
                 const unsigned m = wave_max_u32(tmax);
@@ -830,37 +855,9 @@ void dense_lds_kernel(const DenseSplitArgs A) {
             }
             continue;
         }
-        // max over rows of relu(fma(acc, al, be)) = relu(fma(row max (al >= 0) or min, al, be))
-        float mx = acc[i][0], mn = acc[i][0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) {
-            mx = fmaxf(mx, acc[i][q]);
-            mn = fminf(mn, acc[i][q]);
-        }
-        mx = max_halves(mx);
-        mn = min_halves(mn);
-        const float y = __builtin_fmaf(al >= 0.f ? mx : mn, al, be);
-        const float m = A.norelu ? y : chain_relu(y);
-        // ReLU output >= +0: its bits order as uints; signed (norelu) values go through fkey
-        const unsigned mk = A.norelu ? fkey(m) : __float_as_uint(m);
-        if (h == 0 && slab_row < A.M) {
-            const unsigned gg = (unsigned)slab_row / (unsigned)A.K;
-            if (lds_pool)
-                atomicMax(opool + ((int)gg - row0 / A.K) * TC + lcol, mk);
-            else
-                atomicMax(reinterpret_cast<unsigned *>(A.out + (int64_t)gg * A.ostride + col), mk);
-        }
+        pool_tile(A, slab_row, row0, col, acc[i], al, be, h, lds_pool, opool, TC, lcol);
     }
-    if (lds_pool) {
-        __syncthreads();
-        for (int e = tid; e < gpb * TC; e += 64 * NW) {
-            const int gl = e / TC, c = e - gl * TC;
-            const unsigned gg = (unsigned)(row0 / A.K + gl);
-            if (gg < G)
-                A.out[(int64_t)gg * A.ostride + 32 * ct0 + c] =
-                    A.norelu ? funkey(opool[e]) : __uint_as_float(opool[e]);
-        }
-    }
+    if (lds_pool) flush_lds_pool(A, opool, gpb, TC, row0, ct0, G, tid, 64 * NW);
     PN2_DSTAMP(15);
     PN2_DCLOCK(17);
 }
@@ -966,15 +963,6 @@ static int launch_dense_lds_tile(int tile, const DenseSplitArgs &A, int np, cons
 // Layer 0 is computed once per slice (cs = 2 for 512 outputs: 256 workgroups at SSG's 4096
 // rows).  Products, accumulation order, scales and epilogues are the unfused layers': the same
 // bits (tests/test_gpu_mlp.py).
-template <int NP>
-__device__ __forceinline__ Split load_wfrag(const bf16x8 *wq, int64_t plane) {
-    Split w;
-    w.h = wq[0];
-    w.m = NP >= 2 ? wq[plane] : w.h;
-    w.l = NP == 3 ? wq[2 * plane] : w.h;
-    return w;
-}
-
 #ifndef PN2_PAIR_RD
 #define PN2_PAIR_RD 4
 #endif
@@ -1000,15 +988,7 @@ __global__ __launch_bounds__(64 * kPairWaves) void dense_pair_kernel(const Dense
     const int rb = (int)(lid / (unsigned)cs), slice = (int)(lid % (unsigned)cs);
     const int row0 = 32 * rb;
     const int M = A0.M;
-    if (A1.zero) {  // side job: the next layer's pool
-        const int64_t tot = A1.zrows * A1.zcols, nwg = gridDim.x;
-        const int64_t per = (tot + nwg - 1) / nwg, e0 = (int64_t)blockIdx.x * per;
-        const int64_t e1 = e0 + per < tot ? e0 + per : tot;
-        for (int64_t e = e0 + tid; e < e1; e += 64 * NW) {
-            const int64_t g = e / A1.zcols;
-            A1.zero[g * A1.zstride + (e - g * A1.zcols)] = 0.f;
-        }
-    }
+    zero_share<false>(A1, tid, 64 * NW);
     constexpr int kb0n = KB0, kb1n = KB1;
     const int64_t plane0 = (int64_t)A0.tiles * kb0n * 64, plane1 = (int64_t)A1.tiles * kb1n * 64;
     const bf16x8 *w0 = A0.w + (int64_t)wave * kb0n * 64 + lane;
@@ -1033,13 +1013,8 @@ __global__ __launch_bounds__(64 * kPairWaves) void dense_pair_kernel(const Dense
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int kb = wave + NW * i;
-            if (kb == 0) {  // raw xyz (sample_and_group_all does not centre)
-                const float *prow = A0.pts + (int64_t)b * A0.pb + (int64_t)n * A0.pn;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int ch = (j & 3) + 8 * (j >> 2) + 4 * h;
-                    xa[i][j] = ch < A0.C ? prow[(int64_t)ch * A0.pc] : 0.f;
-                }
+            if (kb == 0) {
+                load_xyz_block(A0.pts + (int64_t)b * A0.pb + (int64_t)n * A0.pn, A0.pc, A0.C, h, xa[i]);
             } else if (kb < kb0n) {
                 const float *f = A0.feat + (int64_t)b * A0.fb + (int64_t)n * A0.fn + 16 * (kb - 1) + 4 * h;
                 const cfloatx4 q0 = *reinterpret_cast<const cfloatx4 *>(f);
@@ -1120,8 +1095,7 @@ __global__ __launch_bounds__(64 * kPairWaves) void dense_pair_kernel(const Dense
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int row = row0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-        const float y = __builtin_fmaf(acc[q], al0, be0);
-        v[q] = A0.raw ? acc[q] * al0 : (A0.norelu ? y : chain_relu(y));
+        v[q] = dense_value(A0, acc[q], al0, be0);
         if (row < M) tmax = max(tmax, __float_as_uint(v[q]) & 0x7FFFFFFFu);
     }
     tmax = wave_max_u32(tmax);
@@ -1190,10 +1164,7 @@ __global__ __launch_bounds__(64 * kPairWaves) void dense_pair_kernel(const Dense
     for (int q = 0; q < 16; ++q) {
         const int row = row0 + (q & 3) + 8 * (q >> 2) + 4 * h;
         if (row < M) {
-            const float y = __builtin_fmaf(acc[q], al1, be1);
-            const float o = A1.raw ? acc[q] * al1 : (A1.norelu ? y : chain_relu(y));
-            A1.out[A1.frag_out ? frag_off(row, col1, 2 * A1.tiles) : (int64_t)row * A1.ostride + col1] = o;
-            omax = max(omax, __float_as_uint(o) & 0x7FFFFFFFu);
+            store_value(A1, row, col1, acc[q], al1, be1, omax);
         }
     }
     if (A1.out_max) {

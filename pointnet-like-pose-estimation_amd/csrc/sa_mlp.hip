@@ -28,6 +28,7 @@
 // Single layers too wide for an LDS-resident tile (e.g. 512 -> 1024 of group_all) use the
 // "dense" kernel: the same wave tiling with A streamed through LDS in 32-deep k chunks.
 #include "pn2_internal.h"
+#include "split_bf16.h"
 
 #include <algorithm>
 #include <cstring>
@@ -64,8 +65,6 @@ struct MlpArgs {
     float *out;
     int64_t ostride;
 };
-
-__device__ __forceinline__ float relu_pos(float t) { return t > 0.f ? t : 0.f; }  // never -0
 
 // ------------------------------------------------------------------ gather
 // act[r][0:D] = features of row r's point, act[r][D:D+C] = xyz (- centroid), 0-pad to cin_pad.
@@ -266,7 +265,7 @@ __device__ __forceinline__ void last_epilogue(const MlpArgs &A, const floatx16 (
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int dr = (r & 3) + 8 * (r >> 2);
-                    if (dr < rem) o[(int64_t)dr * A.ostride] = relu_pos(__builtin_fmaf(acc[i][j][r], al, be));
+                    if (dr < rem) o[(int64_t)dr * A.ostride] = chain_relu(__builtin_fmaf(acc[i][j][r], al, be));
                 }
             }
         } else if (K % 32 == 0) {
@@ -278,7 +277,7 @@ __device__ __forceinline__ void last_epilogue(const MlpArgs &A, const floatx16 (
                 if ((unsigned)(rbase + 32 * j) >= M) break;
                 float t = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) t = fmaxf(t, relu_pos(__builtin_fmaf(acc[i][j][r], al, be)));
+                for (int r = 0; r < 16; ++r) t = fmaxf(t, chain_relu(__builtin_fmaf(acc[i][j][r], al, be)));
                 t = fmaxf(t, __shfl_xor(t, 32));
                 const unsigned g = (unsigned)(rbase + 32 * j) / K;
                 if (A.pool_mode == 0) {  // whole group inside this wave's row block
@@ -300,7 +299,7 @@ __device__ __forceinline__ void last_epilogue(const MlpArgs &A, const floatx16 (
                 float m = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    m = fmaxf(m, relu_pos(__builtin_fmaf(acc[i][j][r], al, be)));
+                    m = fmaxf(m, chain_relu(__builtin_fmaf(acc[i][j][r], al, be)));
                     if ((r + 1) % rpg == 0) {
                         m = fmaxf(m, __shfl_xor(m, 32));
                         const unsigned g = (unsigned)(rbase + 32 * j) / K + r / rpg;
@@ -318,7 +317,7 @@ __device__ __forceinline__ void last_epilogue(const MlpArgs &A, const floatx16 (
                     const unsigned row = rbase + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * h;
                     if (row < M) {
                         const unsigned g = row / K;
-                        const unsigned u = __float_as_uint(relu_pos(__builtin_fmaf(acc[i][j][r], al, be)));
+                        const unsigned u = __float_as_uint(chain_relu(__builtin_fmaf(acc[i][j][r], al, be)));
                         if (LDS_POOL && A.pool_mode == 1) atomicMax(&pool[((int)g - g0) * cw + col], u);
                         else atomicMax(reinterpret_cast<unsigned *>(A.out + (int64_t)g * A.ostride + cb + col), u);
                     }
@@ -369,7 +368,7 @@ __device__ __forceinline__ void run_layer(const MlpArgs &A, const LayerDev &L, f
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (rt0 + j) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    act[row * A.ld + col] = relu_pos(__builtin_fmaf(acc[i][j][r], al, be));
+                    act[row * A.ld + col] = chain_relu(__builtin_fmaf(acc[i][j][r], al, be));
                 }
         }
         __syncthreads();

@@ -33,6 +33,15 @@ struct Split {
 };
 
 __device__ __forceinline__ float chain_relu(float t) { return t > 0.f ? t : 0.f; }  // never -0
+// |x| as uint bits (order-preserving for magnitudes): the NP = 2 activation maxima
+__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+
+// raw s_barrier (__syncthreads' fence would wait vmcnt(0) and drain the DMA ring)
+__device__ __forceinline__ void stage_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 __device__ __forceinline__ Split split8(const float (&x)[8]) {
     Split s;
