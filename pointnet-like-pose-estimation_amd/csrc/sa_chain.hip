@@ -206,10 +206,24 @@ __device__ __forceinline__ Split hid_split(const F8 &x, float up = 1.f) {
         return splitN<NP>(x.v);
     }
 }
-// NP = 2: the wave-uniform scale of a set of activations from the lane's running max of their
-// magnitudes (as uint bits: order-preserving for values >= +0)
-__device__ __forceinline__ ActScale wave_act_scale(unsigned lane_max_bits) {
-    return act_scale(__uint_as_float(wave_max_u32(lane_max_bits)));
+// NP = 2: the scale of a set of activations from the lane's running max of their magnitudes (as
+// uint bits: order-preserving for values >= +0).  Never wider than an 8-row unit, so a row's
+// bits do not depend on which other units share its wave: the compact launch (units of several
+// groups in a wave) and the full launch (32 consecutive rows) scale every row alike.
+// row_act_scale: one scale per row (lanes r and r + 32 hold the row's two halves) -- the
+// transposed layers, whose epilogue has the row's down-scale in its own lane.
+__device__ __forceinline__ ActScale row_act_scale(unsigned lane_max_bits) {
+    const auto p = __builtin_amdgcn_permlane32_swap(lane_max_bits, lane_max_bits, false, false);
+    return act_scale(__uint_as_float(max(p[0], p[1])));
+}
+// unit_act_scale: one scale per 8 rows (lanes 8k .. 8k + 7 of both halves: rows 8k .. 8k + 7 of
+// the slab, a unit of the compact launch and 8 consecutive rows of one group of the full one) --
+// layer 2's input, whose epilogue pools each unit's rows before it scales back.
+__device__ __forceinline__ ActScale unit_act_scale(unsigned v) {
+    v = max(v, PN2_DPP(v, 0xB1));
+    v = max(v, PN2_DPP(v, 0x4E));
+    v = max(v, PN2_DPP(v, 0x141));
+    return row_act_scale(v);
 }
 __device__ __forceinline__ unsigned hid_dep(const Split &x) {
     return __builtin_bit_cast(unsigned, __builtin_shufflevector(x.h, x.h, 0, 1));
@@ -624,7 +638,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
             for (int kb = 0; kb < KB0M; ++kb)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) mb = max(mb, abs_bits(x[kb][j]));
-            const ActScale sc = wave_act_scale(mb);
+            const ActScale sc = row_act_scale(mb);
 #pragma unroll
             for (int kb = 0; kb < KB0M; ++kb)
 #pragma unroll
@@ -695,7 +709,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
         for (int t = 0; t < T1; ++t)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-        // NP = 2: one scale for the wave's layer-1 input (ReLU outputs, >= +0)
+        // NP = 2: one scale per row of the layer-1 input (ReLU outputs, >= +0)
         float up1 = 1.f, asc1 = 1.f;
         if constexpr (NP == 2) {
             unsigned mb = 0;
@@ -703,7 +717,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
             for (int kb = 0; kb < KB1; ++kb)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) mb = max(mb, __float_as_uint(X1[kb].v[j]));
-            const ActScale sc = wave_act_scale(mb);
+            const ActScale sc = row_act_scale(mb);
             up1 = sc.up;
             asc1 = sc.down;
         }
@@ -731,8 +745,8 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
             }
         }
         if constexpr (NP == 2) {
-            // BN + ReLU of every tile in place (fp32), then one scale for the wave's layer-2
-            // input, then the split
+            // BN + ReLU of every tile in place (fp32), then one scale per 8-row unit of the
+            // layer-2 input, then the split
             F8 y[2 * T1];
             unsigned mb = 0;
 #pragma unroll
@@ -742,7 +756,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
                 for (int j = 0; j < 8; ++j)
                     mb = max(mb, max(__float_as_uint(y[2 * t].v[j]), __float_as_uint(y[2 * t + 1].v[j])));
             }
-            const ActScale sc = wave_act_scale(mb);
+            const ActScale sc = unit_act_scale(mb);
             asc2 = sc.down;
 #pragma unroll
             for (int kb = 0; kb < KB2; ++kb) X2[kb] = hid_split<NP>(y[kb], sc.up);
@@ -755,6 +769,14 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
     PN2_STAMP(3);
     // ---- layer 2: standard orientation, pooled over the neighbourhood
     const unsigned G = (unsigned)A.M / (unsigned)A.K;
+    // NP = 2: the down-scale of unit k (rows 8k .. 8k + 7 of the slab), wave-uniform.  A power of
+    // two: scaling a unit's max / min of the accumulator is exact and commutes with them.
+    float dn2[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (NP == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            dn2[k] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(asc2), 8 * k));
+    }
     for (int t = 0; t < L2.tiles; ++t) {
         cfloatx16 acc;
 #pragma unroll
@@ -776,7 +798,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
         // so is relu -- only the row max (al >= 0) or min of the accumulator is needed.
         // Register q of lane half h is row (q&3) + 8(q>>2) + 4h of the slab.
         const int col = 32 * t + r;
-        const float al = NP == 2 ? al2[col] * asc2 : al2[col], be = be2[col];
+        const float al = al2[col], be = be2[col];
         const bool up = al >= 0.f;
         auto fin = [&](float mx, float mn) { return chain_relu(__builtin_fmaf(up ? mx : mn, al, be)); };
         if (compact) {
@@ -803,6 +825,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
                 float mn = fminf(fminf(acc[4 * k], acc[4 * k + 1]), fminf(acc[4 * k + 2], acc[4 * k + 3]));
                 mx = max_halves(mx);
                 mn = min_halves(mn);
+                if constexpr (NP == 2) mx *= dn2[k], mn *= dn2[k];
                 if ((ue >> 8) != sg) {
                     flush();
                     sg = ue >> 8;
@@ -822,6 +845,7 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
                 mn[k] = fminf(fminf(acc[4 * k], acc[4 * k + 1]), fminf(acc[4 * k + 2], acc[4 * k + 3]));
                 mx[k] = max_halves(mx[k]);
                 mn[k] = min_halves(mn[k]);
+                if constexpr (NP == 2) mx[k] *= dn2[k], mn[k] *= dn2[k];
             }
             if (h == 0) {
                 if (A.K == 8) {
@@ -841,11 +865,14 @@ __global__ __launch_bounds__(64 * kChainWaves) __attribute__((amdgpu_waves_per_e
                 }
             }
         } else {
-            float mx = acc[0], mn = acc[0];
+            float mx = 0.f, mn = 0.f;
 #pragma unroll
-            for (int q = 1; q < 16; ++q) {
-                mx = fmaxf(mx, acc[q]);
-                mn = fminf(mn, acc[q]);
+            for (int k = 0; k < 4; ++k) {  // unit k: registers 4k..4k+3 (both halves, merged below)
+                float ux = fmaxf(fmaxf(acc[4 * k], acc[4 * k + 1]), fmaxf(acc[4 * k + 2], acc[4 * k + 3]));
+                float un = fminf(fminf(acc[4 * k], acc[4 * k + 1]), fminf(acc[4 * k + 2], acc[4 * k + 3]));
+                if constexpr (NP == 2) ux *= dn2[k], un *= dn2[k];
+                mx = k ? fmaxf(mx, ux) : ux;
+                mn = k ? fminf(mn, un) : un;
             }
             const float m = fin(max_halves(mx), min_halves(mn));
             const unsigned gg = ((unsigned)slab * 32u) / (unsigned)A.K;
@@ -1301,9 +1328,11 @@ static void chain_fit(ChainPlan &P, const MlpCall &c) {
     // the fp32-accurate chains run split fp16 (3 MFMAs per product, split_bf16.h) where a whole
     // layer-0 input is in registers or pre-transformed (the activation scale needs the wave's
     // whole input); tuning chain_f16 = 0 keeps split bf16 (6 MFMAs)
-    // The activation scale is per wave (32 rows): a cloud's rows must start at a wave boundary
-    // (compact launches: a workgroup per cloud; else S*K a multiple of 32), so a cloud's results
-    // never depend on which other clouds share its batch.
+    // A cloud's rows start at a wave boundary (compact launches: a workgroup per cloud; else S*K
+    // a multiple of 32), so a cloud's results never depend on which other clouds share its
+    // batch.  (The activation scales are per row / per 8-row unit, row_act_scale; the condition
+    // dates from the per-wave scale and is kept: it decides which launches the recorded results
+    // ran split fp16.)
     const bool f16_ok = P.compact || (s.S * K) % 32 == 0;
     P.npk = (c.np == 3 && c.T.chain_f16 && f16_ok && (P.KB0M == 1 || P.KB0M == -1)) ? 2 : c.np;
     const size_t stage_b = P.npk == 3 ? stage_bytes<3>() : P.npk == 2 ? stage_bytes<2>() : stage_bytes<1>();

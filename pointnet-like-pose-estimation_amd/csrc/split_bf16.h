@@ -13,11 +13,14 @@
 // two 1 KB weight planes per step instead of three.  fp16's exponent range is narrow, so both
 // operands are scaled by powers of two first (exact): each weight row (output channel) so that
 // its largest |w| lies in [2^14, 2^15) (pack_split_kernel; the inverse scale is folded into the
-// BN scale), each wave's 32 activation rows by one wave-uniform factor that puts their largest
-// |x| in [2^14, 2^15) (act_scale; folded into the consuming layer's BN scale likewise).  Scaling
-// by 2^k commutes with fp32 rounding, so the result is that of an unbounded-exponent split;
-// values more than 2^17 below their wave's / row's maximum lose relative precision, but their
-// absolute error stays below 2^-39 of that maximum.
+// BN scale), the activation rows by one factor per scaling set that puts the set's largest |x|
+// in [2^14, 2^15) (act_scale; folded into the consuming layer's BN scale likewise): a wave's 32
+// rows in the dense layers; in the chain kernel one row (the transposed layers) or one 8-row
+// unit (layer 2's input), so that a row's bits never depend on the units that share its wave
+// (sa_chain.hip row_act_scale / unit_act_scale).  Scaling by 2^k commutes with fp32 rounding,
+// so the result is that of an unbounded-exponent split; values more than 2^17 below their
+// set's / row's maximum lose relative precision (the low plane becomes an fp16 subnormal), but
+// their absolute error stays below 2^-39 of that maximum.
 #pragma once
 #include <hip/hip_runtime.h>
 
