@@ -44,6 +44,12 @@
  *                                                            translation_ssg.py:23-26
  *   pn2_fc_bn_forward_rows_f32 / pn2_fc_bn_backward_rows_f32
  *                          the same for batches above 64 rows (the scripts' --batch_size)
+ *   pn2_transform_points_f32 / pn2_transform_points_backward_f32
+ *                          torch.bmm of a T-Net's transform with the points under autograd
+ *                                                            model/pointnet_utils.py:102-113, 120-123;
+ *                                                            pose.py:50-69
+ *   pn2_orthogonality_forward_f32 / pn2_orthogonality_backward_f32
+ *                          feature_transform_reguliarzer     model/pointnet_utils.py:140-147
  *   pn2_bn_train_stats_f32 / pn2_bn_relu_apply_f32 (/ pn2_bn_train_forward_f32: both) /
  *   pn2_group_max_f32 / pn2_bn_relu_backward_f32
  *                          train-mode BatchNorm2d + ReLU + torch.max over K, forward and backward
@@ -536,6 +542,84 @@ int pn2_criterion_backward_f32(int kind, int reduction, const float *P, int64_t 
 int pn2_meter_update(int kind, const void *pred, int64_t ldp, const void *target, int64_t ldt,
                      const int64_t *label, int64_t B, int64_t D, int64_t num_category, double *acc,
                      double *invalid, double *records, int64_t slot, int64_t slots, void *stream);
+
+/* ---- the PointNet-v1 per-cloud transforms and their orthogonality regulariser under autograd
+ * (csrc/v1_transform.hip), forward and backward, every sum in a stated order.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * Reference: torch.bmm of the 3x3 input transform and the 64x64 feature transform with the
+ * points, model/pointnet_utils.py:102-113, 120-123 and pose.py:50-69, and
+ * feature_transform_reguliarzer, pointnet_utils.py:140-147, under the training loops' autograd.
+ * Every entry is async on the caller's stream and graph-capturable, uses no float atomics, and
+ * no workgroup waits for, or reads, another's result within a launch.  The unit is compiled
+ * without contraction: an fma is only where a rule says "fma" (one rounding per step), every
+ * other operation rounds on its own.  1 <= k <= 64 (the reference uses 3 and 64).
+ *
+ * Tensors of points -- x, y, dy, dx: [B][N][k] float32 -- are read and written in place through
+ * ELEMENT strides (sb, sn, sc) >= 0: a channel-first [B][k][N] tensor is (k*N, 1, N), rows
+ * [B][N][k] are (N*k, k, 1); any other view works too.  16-byte accesses are used only where a
+ * tensor's base address, its strides and k allow them (unit sc with k, sn, sb multiples of 4, or
+ * unit sn with sc, sb multiples of 4, and a 16-byte aligned base), dword accesses otherwise; no
+ * access passes an edge.  T is [B][k][k] float32 with row stride ldt >= k (cloud b at
+ * T + b*k*ldt).  dT, G are dense [B][k][k].
+ *
+ * pn2_transform_points_f32: y[b][n][i] = sum_j T[b][i][j] * x[b][n][j].
+ *   THE RULE: each element is ONE float32 chain acc = fma(T[b][i][j], x[b][n][j], acc) over
+ *   j = 0 .. k-1 from +0.0f.  ROW INDEPENDENCE: y[b][n][:] is a function of x[b][n][:] and of
+ *   T[b] only -- not of N, B, the strides, the access width or the row's position.
+ * pn2_transform_points_backward_f32: dy, and x (for dT), T (for dx) -> dx and dT; either output
+ *   may be NULL and is then skipped (with what only it reads).  Every element of a non-NULL
+ *   output is written: the buffers may hold anything.
+ *   THE dx RULE: dx[b][n][j] = sum_i dy[b][n][i] * T[b][i][j], ONE float32 fma chain over
+ *   i = 0 .. k-1 from +0.0f; row independent as the forward.
+ *   THE dT RULE:
+ *   1. the N rows of a cloud are cut into slabs of R = pn2_transform_slab_rows() rows, a
+ *      constant of the build (a function of nothing): slab s holds rows [s*R, min((s+1)*R, N));
+ *   2. slab s gives, per (i, j), the float64 partial P_s = sum_n double(dy[b][n][i]) *
+ *      double(x[b][n][j]) over its rows in ascending n from +0.0 (each product is exact in
+ *      float64; one rounding per add);
+ *   3. dT[b][i][j] = float32(sum_s P_s) in ascending s from +0.0 in float64, rounded once.
+ *   dT[b] therefore depends on cloud b's rows only -- not on B or on the other clouds.
+ *   One launch writes the partials to `workspace` (8-byte aligned), a second one reduces them.
+ *   pn2_transform_workspace_bytes(B, N, k) = B * ceil(N/R) * k * k * 8 bytes exactly (-1: bad
+ *   arguments).  No workspace is needed (NULL, 0) when dT is NULL.
+ *
+ * pn2_orthogonality_forward_f32: T -> norm [B], loss (one float32), and G [B][k][k] when G is
+ *   not NULL.
+ *     G[b] = T[b] T[b]^T - I: G[b][i][j] is ONE float32 chain acc = fma(T[b][i][l], T[b][j][l],
+ *       acc) over l = 0 .. k-1 from +0.0f, then one float32 subtraction of 1 where i == j.  The
+ *       fma is symmetric in its two factors, so G[b] is BITWISE SYMMETRIC.
+ *     norm[b] = float32(sqrt(sum double(G[b][i][j])^2)): ONE float64 chain over (i, j) in
+ *       row-major order from +0.0 (each square exact), a correctly rounded float64 sqrt.
+ *     loss = float32((sum_b double(norm[b])) / B), ascending b from +0.0.
+ *   Two launches: the clouds side by side, then the mean.  norm is what the backward reads.
+ * pn2_orthogonality_backward_f32: T, the forward's norm, dloss (a DEVICE pointer to the
+ *   upstream float32 scalar) -> dT[b] = c_b * (G[b] T[b]):
+ *     G[b] recomputed under the forward's rule;
+ *     (G T)[i][j] ONE float32 chain acc = fma(G[b][i][l], T[b][l][j], acc) over l = 0 .. k-1
+ *       from +0.0f, then one float32 multiplication by c_b;
+ *     c_b = float32((2.0 * double(dloss)) / (double(B) * double(norm[b]))), rounded once.
+ *   norm[b] == 0 (T[b] T[b]^T == I exactly): c_b = +0.0f, so dT[b] is all zeros -- what torch's
+ *   CPU backward of torch.norm(..., dim=(1, 2)) gives at a zero matrix (it fills the norm's
+ *   subgradient with zeros there instead of dividing by the norm).
+ *
+ * Errors, before any device call: PN2_EINVAL for B < 1, N < 1, k < 1, a negative stride, ldt
+ * below k, a NULL required pointer (dx and dT both NULL included), a workspace that is too small
+ * or not 8-byte aligned; PN2_EUNSUPPORTED for k > 64, B or N above 2^30, more than 2^31 - 1
+ * 64-row tiles in all. */
+int64_t pn2_transform_slab_rows(void);
+int64_t pn2_transform_workspace_bytes(int64_t B, int64_t N, int64_t k);
+int pn2_transform_points_f32(const float *x, int64_t xsb, int64_t xsn, int64_t xsc, const float *T,
+                             int64_t ldt, float *y, int64_t ysb, int64_t ysn, int64_t ysc, int64_t B,
+                             int64_t N, int64_t k, void *stream);
+int pn2_transform_points_backward_f32(const float *dy, int64_t dsb, int64_t dsn, int64_t dsc,
+                                      const float *x, int64_t xsb, int64_t xsn, int64_t xsc,
+                                      const float *T, int64_t ldt, float *dx, int64_t gsb, int64_t gsn,
+                                      int64_t gsc, float *dT, int64_t B, int64_t N, int64_t k,
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+int pn2_orthogonality_forward_f32(const float *T, int64_t ldt, int64_t B, int64_t k, float *G, float *norm,
+                                  float *loss, void *stream);
+int pn2_orthogonality_backward_f32(const float *T, int64_t ldt, const float *norm, const float *dloss,
+                                   int64_t B, int64_t k, float *dT, void *stream);
 
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]

@@ -125,6 +125,14 @@ SIGNATURES = {
     "pn2_criterion_backward_f32": (_int, [_int, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "pn2_meter_update": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
                                 _vp]),
+    "pn2_transform_slab_rows": (_i64, []),
+    "pn2_transform_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "pn2_transform_points_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64,
+                                        _i64, _vp]),
+    "pn2_transform_points_backward_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp,
+                                                 _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pn2_orthogonality_forward_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pn2_orthogonality_backward_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),

@@ -25,8 +25,8 @@ from . import tuning
 from .pointnet2_utils import _needs_autograd
 from .losses import head_log_softmax
 from .train import linear_bn_train
-from .pointnet_utils import (PointNetEncoder, TNet3d, TNetkd, _rows_to_cf, linear_bn, mlp_mode,
-                             run_mlp)
+from .pointnet_utils import (PointNetEncoder, TNet3d, TNetkd, _rows_to_cf, apply_transform, linear_bn,
+                             mlp_mode, run_mlp)
 
 
 class _ConvStack(nn.Module):
@@ -213,16 +213,16 @@ class PoseV1(_ConvStack):
             if D > 3:
                 normal = x[:, 3:, :]
                 x = x[:, :3, :]
-            x = torch.bmm(transform, x)
+            x = apply_transform(self, transform, x)
             if D > 3:
                 x = torch.cat([x, normal], dim=2)  # the reference's axis (pose.py:57)
         mode = self._mode(x)
         if self.feat_trans:
             h, trans_feat = self._split_ftnet(x, mode)
             if mode != "torch":  # bmm(trans_feat, x) in the rows layout
-                h = torch.bmm(h, trans_feat.transpose(1, 2))
+                h = apply_transform(self, trans_feat, h, rows=True)
             else:
-                h = torch.bmm(trans_feat, h)
+                h = apply_transform(self, trans_feat, h)
             x = self._layers(h, 2, len(self.conv), True, mode, rows=mode != "torch")
         else:
             x = self._layers(x, 0, len(self.conv), True, mode)

@@ -28,6 +28,11 @@ Ops (reference code each replaces, in /root/reference/model/pointnet2_utils.py):
                       (model/pointnet2_cls_ssg.py:36, 40-47, rotation_ssg.py:40-50,
                       sign_ssg.py:38-45) and the test loops' per-class bookkeeping
                       (train_rotation.py:157-163), every sum in a fixed order
+  pn2::transform_points / transform_points_backward  torch.bmm of a T-Net's transform with the
+                      points under autograd (model/pointnet_utils.py:102-113,
+                      120-123; pose.py:50-69), forward, dx and dT in stated orders
+  pn2::orthogonality_forward / orthogonality_backward  feature_transform_reguliarzer
+                      (pointnet_utils.py:140-147) and its gradient
   pn2::bn_relu_group_max  eval BatchNorm2d + ReLU + torch.max of the last MLP layer :170-172 on
                       channels-last rows (the recompute of pn2.train's frozen mode)
 """
@@ -1188,3 +1193,184 @@ bn_relu_group_max = torch.library.custom_op("pn2::bn_relu_group_max", bn_relu_gr
 def _(Y, K, mean, invstd, gamma, beta, relu):
     G = Y.shape[0] // K
     return Y.new_empty(G, Y.shape[1]), Y.new_empty(G, Y.shape[1], dtype=torch.int32)
+
+
+# ------------------------------------------------------------------------------ v1 transforms
+TRANSFORM_MAX_K = 64
+
+
+def transform_slab_rows() -> int:
+    """R of pn2_transform_points_backward_f32's dT rule (a constant of the build)."""
+    return int(_L.pn2_transform_slab_rows())
+
+
+def _cloud(t: Tensor, rows: bool, what: str):
+    """A tensor of points, rows [B,N,k] or channel-first [B,k,N], as the transform kernels read it
+    in place -> (B, N, k, (sb, sn, sc) element strides of the [B][N][k] view)."""
+    _dev(t, what)
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise TypeError("%s: 3-D float32 tensors of points" % what)
+    v = t if rows else t.permute(0, 2, 1)
+    return v.shape[0], v.shape[1], v.shape[2], tuple(v.stride())
+
+
+def _transforms(T: Tensor, B: int, k: int, what: str) -> Tuple[Tensor, int]:
+    """T [B,k,k] as the kernels read it -> (tensor, row stride): unit column stride, a row
+    stride >= k and clouds k rows apart; any other view is copied."""
+    if T.dtype != torch.float32 or tuple(T.shape) != (B, k, k):
+        raise ValueError("%s: T [B,k,k] float32, one transform per cloud" % what)
+    if not 1 <= k <= TRANSFORM_MAX_K:
+        raise ValueError("%s: k=%d outside [1, %d]" % (what, k, TRANSFORM_MAX_K))
+    if T.stride(2) != 1 or T.stride(1) < k or T.stride(0) != k * T.stride(1):
+        T = T.contiguous()
+    return T, T.stride(1)
+
+
+def _like_cloud(B: int, N: int, k: int, rows: bool, like: Tensor):
+    """A fresh dense tensor in the caller's layout and its [B][N][k] element strides."""
+    if rows:
+        return torch.empty(B, N, k, dtype=torch.float32, device=like.device), (N * k, k, 1)
+    return torch.empty(B, k, N, dtype=torch.float32, device=like.device), (k * N, 1, N)
+
+
+def transform_points_direct(x: Tensor, T: Tensor, rows: bool) -> Tensor:
+    """x rows [B,N,k] (rows) or channel-first [B,k,N] (any strides, read in place), T [B,k,k]
+    -> y in x's layout, y[b,n,:] = T[b] x[b,n,:]: torch.bmm(T, x) of a channel-first x,
+    torch.bmm(x, T^T) of rows (pn2_transform_points_f32: each element one float32 fma chain over
+    ascending j; a row's result depends on that row and T[b] only)."""
+    what = "pn2::transform_points"
+    B, N, k, (sb, sn, sc) = _cloud(x, rows, what)
+    T, ldt = _transforms(T, B, k, what)
+    y, (yb, yn, yc) = _like_cloud(B, N, k, rows, x)
+    if B * N == 0:
+        return y
+    _run("pn2_transform_points_f32", _L.pn2_transform_points_f32,
+         (x.data_ptr(), sb, sn, sc, T.data_ptr(), ldt, y.data_ptr(), yb, yn, yc, B, N, k, _stream(x)), x.device,
+         flops=2.0 * B * N * k * k, nbytes=4.0 * (2 * B * N * k + B * k * k))
+    return y
+
+
+transform_points = torch.library.custom_op("pn2::transform_points", transform_points_direct, mutates_args=())
+
+
+@transform_points.register_fake
+def _(x, T, rows):
+    return x.new_empty(x.shape)
+
+
+def transform_points_backward_direct(dy: Tensor, x: Optional[Tensor], T: Optional[Tensor], rows: bool,
+                                     need_dx: bool = True, need_dT: bool = True):
+    """The backward of transform_points_direct: dy in the forward's layout (any strides), the
+    forward's x (read for dT only) and T (read for dx only) -> (dx in that layout or None,
+    dT [B,k,k] or None).  pn2_transform_points_backward_f32: dx one float32 fma chain over
+    ascending i per element; dT float64 partials of transform_slab_rows()-row slabs in ascending
+    n, added in ascending slab order and rounded once.  The partials live in ops' per-stream
+    workspace."""
+    what = "pn2::transform_points_backward"
+    B, N, k, (db, dn, dc) = _cloud(dy, rows, what)
+    if not (need_dx or need_dT):
+        return None, None
+    xb = xn = xc = ldt = 0
+    if need_dT:
+        if x is None or _cloud(x, rows, what)[:3] != (B, N, k) or x.device != dy.device:
+            raise ValueError("%s: x in dy's shape on dy's device" % what)
+        xb, xn, xc = _cloud(x, rows, what)[3]
+    if need_dx:
+        if T is None or T.device != dy.device:
+            raise ValueError("%s: T [B,k,k] on dy's device" % what)
+        T, ldt = _transforms(T, B, k, what)
+    elif not 1 <= k <= TRANSFORM_MAX_K:
+        raise ValueError("%s: k=%d outside [1, %d]" % (what, k, TRANSFORM_MAX_K))
+    dx, (gb, gn, gc) = _like_cloud(B, N, k, rows, dy) if need_dx else (None, (0, 0, 0))
+    dT = torch.empty(B, k, k, dtype=torch.float32, device=dy.device) if need_dT else None
+    if B * N == 0:
+        return dx, (dT.zero_() if need_dT else None)
+    st = _stream(dy)
+    nbytes = int(_L.pn2_transform_workspace_bytes(B, N, k)) if need_dT else 0
+    if nbytes < 0:
+        raise ValueError("%s: bad shape B=%d N=%d k=%d" % (what, B, N, k))
+    ws = _workspace(nbytes, dy.device, st) if need_dT else None
+    _run("pn2_transform_points_backward_f32", _L.pn2_transform_points_backward_f32,
+         (dy.data_ptr(), db, dn, dc, x.data_ptr() if need_dT else 0, xb, xn, xc,
+          T.data_ptr() if need_dx else 0, ldt, dx.data_ptr() if need_dx else 0, gb, gn, gc,
+          dT.data_ptr() if need_dT else 0, B, N, k, ws.data_ptr() if need_dT else 0,
+          ws.numel() if need_dT else 0, st), dy.device,
+         flops=2.0 * B * N * k * k * (int(need_dx) + int(need_dT)),
+         nbytes=4.0 * B * N * k * (1 + int(need_dx) + int(need_dT)) + 2.0 * nbytes)
+    return dx, dT
+
+
+def _transform_points_backward_op(dy: Tensor, x: Tensor, T: Tensor, rows: bool) -> Tuple[Tensor, Tensor]:
+    return transform_points_backward_direct(dy, x, T, rows)
+
+
+transform_points_backward = torch.library.custom_op("pn2::transform_points_backward",
+                                                    _transform_points_backward_op, mutates_args=())
+
+
+@transform_points_backward.register_fake
+def _(dy, x, T, rows):
+    return dy.new_empty(dy.shape), T.new_empty(T.shape)
+
+
+def orthogonality_forward_direct(T: Tensor, want_G: bool = False):
+    """T [B,k,k] -> (loss 0-dim, norm [B], G [B,k,k] or None): feature_transform_reguliarzer's
+    mean_b ||T[b] T[b]^T - I||_F (pn2_orthogonality_forward_f32: G one float32 fma chain per
+    element, bitwise symmetric; each norm one float64 chain in row-major order; the mean one
+    float64 chain over ascending b)."""
+    what = "pn2::orthogonality_forward"
+    _dev(T, what)
+    if T.dim() != 3 or T.shape[1] != T.shape[2] or T.shape[0] < 1:
+        raise ValueError("%s: T [B,k,k], B >= 1" % what)
+    B, k = T.shape[0], T.shape[1]
+    T, ldt = _transforms(T, B, k, what)
+    loss = torch.empty((), dtype=torch.float32, device=T.device)
+    norm = torch.empty(B, dtype=torch.float32, device=T.device)
+    G = torch.empty(B, k, k, dtype=torch.float32, device=T.device) if want_G else None
+    _run("pn2_orthogonality_forward_f32", _L.pn2_orthogonality_forward_f32,
+         (T.data_ptr(), ldt, B, k, G.data_ptr() if want_G else 0, norm.data_ptr(), loss.data_ptr(), _stream(T)),
+         T.device, flops=2.0 * B * k * k * k, nbytes=4.0 * B * k * k)
+    return loss, norm, G
+
+
+def _orthogonality_forward_op(T: Tensor) -> Tuple[Tensor, Tensor]:
+    return orthogonality_forward_direct(T)[:2]
+
+
+orthogonality_forward = torch.library.custom_op("pn2::orthogonality_forward", _orthogonality_forward_op,
+                                                mutates_args=())
+
+
+@orthogonality_forward.register_fake
+def _(T):
+    return T.new_empty(()), T.new_empty(T.shape[0])
+
+
+def orthogonality_backward_direct(T: Tensor, norm: Tensor, dloss: Tensor) -> Tensor:
+    """T [B,k,k], the forward's norm [B], dloss (a one-element float32 device tensor) ->
+    dT[b] = c_b * (G[b] T[b]), c_b = 2 dloss / (B norm[b]) evaluated in float64, +0 where
+    norm[b] == 0 (pn2_orthogonality_backward_f32)."""
+    what = "pn2::orthogonality_backward"
+    _dev(T, what)
+    if T.dim() != 3 or T.shape[1] != T.shape[2] or T.shape[0] < 1:
+        raise ValueError("%s: T [B,k,k], B >= 1" % what)
+    B, k = T.shape[0], T.shape[1]
+    T, ldt = _transforms(T, B, k, what)
+    if (norm.dtype != torch.float32 or tuple(norm.shape) != (B,) or norm.device != T.device or
+            dloss.dtype != torch.float32 or dloss.numel() != 1 or dloss.device != T.device):
+        raise ValueError("%s: norm [B] and a one-element dloss, float32 on T's device" % what)
+    norm = norm.contiguous()
+    dT = torch.empty(B, k, k, dtype=torch.float32, device=T.device)
+    _run("pn2_orthogonality_backward_f32", _L.pn2_orthogonality_backward_f32,
+         (T.data_ptr(), ldt, norm.data_ptr(), dloss.data_ptr(), B, k, dT.data_ptr(), _stream(T)), T.device,
+         flops=4.0 * B * k * k * k, nbytes=8.0 * B * k * k)
+    return dT
+
+
+orthogonality_backward = torch.library.custom_op("pn2::orthogonality_backward", orthogonality_backward_direct,
+                                                 mutates_args=())
+
+
+@orthogonality_backward.register_fake
+def _(T, norm, dloss):
+    return T.new_empty(T.shape)

@@ -122,8 +122,18 @@ def fused_eval(enabled=True):
 def eval_autograd(enabled=True):
     """Round-2 name kept for callers: eval-mode forwards with autograd enabled are
     differentiable (the default now); ``enabled=False`` is ``fused_eval()``."""
-    with fused_eval(not enabled):
-        yield
+    prev = getattr(_fused, "reference", False)
+    _fused.reference = bool(enabled)  # the v1 modules keep the reference's formulation inside it
+    try:
+        with fused_eval(not enabled):
+            yield
+    finally:
+        _fused.reference = prev
+
+
+def _in_eval_autograd():
+    """Whether this thread is inside ``eval_autograd()``."""
+    return getattr(_fused, "reference", False)
 
 
 def _needs_autograd(module, *tensors):

@@ -18,13 +18,19 @@ with a group_all source for a channel-first [B,C<=16,N] input, or a rows source 
 features already in HBM), one launch per layer, the max fused into the last layer's epilogue;
 the encoder's conv3 + bn3 without ReLU before its max uses PN2_LAYER_NO_RELU (signed pooling).
 The small per-cloud transforms (torch.bmm of a 3x3 / 64x64 matrix with the points) and the
-T-Nets' FC layers are plain library GEMMs (torch on the GPU).  Training on the GPU runs the same
-shared MLPs through pn2.train.point_mlp_train (library GEMMs + the fused batch-statistics BN /
-ReLU / max kernels, forward and backward) in the same rows layout; eval with autograd (and
-exotic BN configurations) keeps the reference's torch formulation.  With tuning key
-train_head=1 the T-Nets' FC tail under autograd (fc1/bn4, fc2/bn5, fc3) runs on the kernels of
-csrc/fc_train.hip (pn2.train.linear_bn_train); the ``+ iden`` stays a torch add and the bmm
-transforms stay library calls.
+T-Nets' FC layers are plain library GEMMs (torch on the GPU) in the no_grad forward.  Training
+on the GPU runs the same shared MLPs through pn2.train.point_mlp_train (library GEMMs, or the
+train_gemm kernels, + the fused batch-statistics BN / ReLU / max kernels, forward and backward)
+in the same rows layout.  Eval with autograd keeps the reference's torch formulation by default
+(as do exotic BN configurations); with tuning key v1_eval_grad=1 it is mlp_mode's fourth answer,
+"eval_grad": the fused kernels forward -- the no_grad launches and bits -- inside _V1EvalGrad,
+which saves the MLP's input only and recomputes the MLP on pn2.train.point_mlp_frozen in its
+backward.  With tuning key train_head=1 the T-Nets' FC tail under autograd (fc1/bn4, fc2/bn5,
+fc3) runs on the kernels of csrc/fc_train.hip (pn2.train.linear_bn_train); the ``+ iden`` stays
+a torch add.  With tuning key v1_transform=1 the transforms of a differentiable forward
+(apply_transform: train mode and eval under autograd, float32 device tensors, k <= 64) run
+pn2.train.transform_points and feature_transform_reguliarzer runs pn2.train.orthogonality_loss
+(csrc/v1_transform.hip: every sum in a stated order, forward and backward); torch.bmm otherwise.
 """
 import numpy as np
 import torch
@@ -35,7 +41,7 @@ from . import _lib
 from . import ops
 from . import train
 from . import tuning
-from .pointnet2_utils import _needs_autograd, _precision
+from .pointnet2_utils import _in_eval_autograd, _needs_autograd, _precision, _versions
 
 
 # ----------------------------------------------------------------------------- eval-mode MLPs
@@ -102,25 +108,106 @@ def point_mlp(x, convs, bns, cache, pool=True, last_relu=True, module=None, rows
     return out if pool else out.view(B, N, cout)
 
 
+def _eval_grad_route(module, x, convs, bns):
+    """Whether an eval-mode v1 shared MLP that must be differentiable runs the fused inference
+    kernels with the recompute backward (_V1EvalGrad): tuning key v1_eval_grad=1, outside
+    pn2.eval_autograd(), float32 device tensors, fp32 arithmetic, widths the fused entry takes
+    and layers the frozen-statistics kernels cover."""
+    if module.training or tuning.get("v1_eval_grad") != 1 or _in_eval_autograd():
+        return False
+    if not x.is_cuda or x.dtype != torch.float32 or _precision(module) != "fp32":
+        return False
+    if not all(ops.sa_mlp_supported([c.weight.shape[0]]) for c in convs):
+        return False
+    return train.eligible_frozen(x, convs, bns)
+
+
 def mlp_mode(module, x, convs, bns):
     """How a v1 module runs its shared MLPs on x: "fused" (eval without autograd: the split-bf16
-    kernels; a CPU tensor raises), "train" (training on the device: pn2.train), or "torch" (the
-    reference's formulation: eval with autograd, CPU training, BN configs pn2.train does not
+    kernels; a CPU tensor raises), "train" (training on the device: pn2.train), "eval_grad" (eval
+    with autograd under tuning key v1_eval_grad=1: the fused kernels forward, the frozen
+    training kernels recomputing in the backward -- _V1EvalGrad) or "torch" (the reference's
+    formulation: eval with autograd otherwise, CPU training, BN configs pn2.train does not
     cover)."""
     if not _needs_autograd(module, x):
         return "fused"
     if module.training and train.eligible(x, convs, bns):
         return "train"
+    if _eval_grad_route(module, x, convs, bns):
+        return "eval_grad"
     return "torch"
 
 
+class _V1EvalGrad(torch.autograd.Function):
+    """A v1 shared MLP's eval-mode forward under autograd (modelled on pointnet2_utils
+    _SaEvalGrad): the forward is point_mlp as it is -- the launches and the bits of the no_grad
+    call on the same input; nothing of the MLP is saved, only the input and the module's
+    versions.  The backward recomputes the MLP on the frozen-statistics training kernels
+    (train.point_mlp_frozen) and backpropagates through that: gradients of the reference's eval
+    formulation (Conv1d + BatchNorm1d on its running statistics) for the input and the conv / BN
+    parameters."""
+
+    @staticmethod
+    def forward(ctx, module, convs, bns, cache, pool, last_relu, rows, x, *params):
+        out = point_mlp(x, convs, bns, cache, pool, last_relu, module, rows)
+        ctx.module, ctx.convs, ctx.bns = module, convs, bns  # the recompute reads the live parameters
+        ctx.cfg = (pool, last_relu, rows)
+        ctx.versions = _versions(module)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        module = ctx.module
+        if _versions(module) != ctx.versions:
+            raise RuntimeError("pn2: a parameter or buffer of %s was modified in place, or the module "
+                               "left eval mode, between the eval-mode forward and its backward (the "
+                               "backward recomputes the layer from them)" % type(module).__name__)
+        x, = ctx.saved_tensors
+        pool, last_relu, rows = ctx.cfg
+        params = _mlp_params(ctx.convs, ctx.bns)
+        with torch.enable_grad():
+            leaf = x.detach().requires_grad_(ctx.needs_input_grad[7])
+            out = train.point_mlp_frozen(leaf, ctx.convs, ctx.bns, rows, pool, last_relu)
+            wanted = [i for i in range(len(params)) if ctx.needs_input_grad[8 + i]]
+            inputs = [params[i] for i in wanted] + ([leaf] if leaf.requires_grad else [])
+            got = torch.autograd.grad([out], inputs, [dout.reshape(out.shape)], allow_unused=True)
+        grads = [None] * len(params)
+        for i, g in zip(wanted, got):
+            grads[i] = g
+        dx = got[-1] if leaf.requires_grad else None
+        return (None,) * 7 + (dx,) + tuple(grads)
+
+
+def _mlp_params(convs, bns):
+    params = []
+    for conv, bn in zip(convs, bns):
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    return params
+
+
 def run_mlp(mode, x, convs, bns, cache, pool=True, last_relu=True, module=None, rows=False):
-    """point_mlp ("fused") or train.point_mlp_train ("train") on x: channel-first [B, C, N]
-    as the module received it (rows=False), or rows [B, N, C] from a previous run_mlp
-    (rows=True).  Same results layout: [B, cout] (pool) or rows [B, N, cout]."""
+    """point_mlp ("fused"), train.point_mlp_train ("train") or _V1EvalGrad ("eval_grad") on x:
+    channel-first [B, C, N] as the module received it (rows=False), or rows [B, N, C] from a
+    previous run_mlp (rows=True).  Same results layout: [B, cout] (pool) or rows [B, N, cout]."""
     if mode == "train":
         return train.point_mlp_train(x, convs, bns, rows, pool, last_relu)
+    if mode == "eval_grad":
+        return _V1EvalGrad.apply(module, convs, bns, cache, pool, last_relu, rows, x, *_mlp_params(convs, bns))
     return point_mlp(x, convs, bns, cache, pool, last_relu, module, rows)
+
+
+def apply_transform(module, T, x, rows=False):
+    """A T-Net's per-cloud transform of the points: ``torch.bmm(T, x)`` of a channel-first
+    x [B, k, N] (pointnet_utils.py:108, 122), ``torch.bmm(x, T^T)`` of rows [B, N, k].  With
+    tuning key v1_transform=1, where the forward must be differentiable on float32 device
+    tensors with k <= 64, it is train.transform_points (csrc/v1_transform.hip); torch.bmm
+    everywhere else."""
+    if (tuning.get("v1_transform") == 1 and _needs_autograd(module, x, T) and
+            train.transform_eligible(x, T)):
+        return train.transform_points(x, T, rows)
+    return torch.bmm(x, T.transpose(1, 2)) if rows else torch.bmm(T, x)
 
 
 def _fold_linear(fc, bn, cache, extra=None):
@@ -277,14 +364,14 @@ class PointNetEncoder(nn.Module):
         if D > 3:
             normal = x[:, 3:, :]
             x = x[:, :3, :]
-        x = torch.bmm(transform, x)
+        x = apply_transform(self, transform, x)
         if D > 3:
             x = torch.cat([x, normal], dim=2)  # the reference's concatenation axis (:112)
         mode = mlp_mode(self, x, [self.conv1, self.conv2, self.conv3], [self.bn1, self.bn2, self.bn3])
         if mode == "torch":
             x = F.relu(self.bn1(self.conv1(x)))
             trans_feat = self.ftnet(x)
-            x = torch.bmm(trans_feat, x)
+            x = apply_transform(self, trans_feat, x)
             pointfeat = x
             x = F.relu(self.bn2(self.conv2(x)))
             x = self.bn3(self.conv3(x))
@@ -294,7 +381,7 @@ class PointNetEncoder(nn.Module):
             r1 = run_mlp(mode, x, [self.conv1], [self.bn1], self._c1, pool=False, module=self)
             trans_feat = self.ftnet(_rows_to_cf(r1))
             # bmm(trans_feat, x) in the rows layout: x2 rows = x1 rows . trans_feat^T
-            r2 = torch.bmm(r1, trans_feat.transpose(1, 2))
+            r2 = apply_transform(self, trans_feat, r1, rows=True)
             pointfeat = _rows_to_cf(r2)
             # conv2 + bn2 + relu, conv3 + bn3 (no ReLU, :126-127), max over the points
             x = run_mlp(mode, r2, [self.conv2, self.conv3], [self.bn2, self.bn3], self._c23,
@@ -308,9 +395,13 @@ class PointNetEncoder(nn.Module):
 def feature_transform_reguliarzer(transform):
     """pointnet_utils.py:140-147 (name kept as spelled in the reference)."""
     d = transform.size()[1]
+    if (tuning.get("v1_transform") == 1 and torch.is_grad_enabled() and transform.requires_grad and
+            transform.dim() == 3 and transform.is_cuda and transform.dtype == torch.float32 and
+            transform.size()[2] == d and 1 <= d <= ops.TRANSFORM_MAX_K):
+        return train.orthogonality_loss(transform)  # csrc/v1_transform.hip, every sum in a stated order
     I = torch.eye(d, device=transform.device)[None, :, :]
     return torch.mean(torch.norm(torch.bmm(transform, transform.transpose(2, 1)) - I, dim=(1, 2)))
 
 
 __all__ = ["TNet3d", "TNetkd", "PointNetEncoder", "feature_transform_reguliarzer", "point_mlp",
-           "mlp_mode", "run_mlp", "linear_bn"]
+           "mlp_mode", "run_mlp", "linear_bn", "apply_transform"]

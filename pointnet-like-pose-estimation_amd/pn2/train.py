@@ -32,8 +32,15 @@ invstd = rsqrt(running_var + eps), constants of the backward (PN2_LAYER_FROZEN_S
 running-stat update, no counter increment.  Hidden layers run pn2_bn_relu_apply_f32; the pooled
 last layer runs pn2_bn_relu_group_max_f32, which keeps Y and never writes its activation.  The
 SA modules' eval-mode forward under autograd recomputes a layer with it in its backward
-(pn2/pointnet2_utils.py); the v1 modules' eval forward with autograd keeps the reference's
-torch formulation.
+(pn2/pointnet2_utils.py); with tuning key v1_eval_grad=1 the v1 modules' eval forward under
+autograd does the same on point_mlp_frozen (pn2/pointnet_utils._V1EvalGrad), and keeps the
+reference's torch formulation otherwise.
+
+The v1 per-cloud transforms and regulariser (transform_points, orthogonality_loss; tuning key
+v1_transform=1): torch.bmm of a T-Net's [B, k, k] output with the points, and
+feature_transform_reguliarzer, forward and backward on the kernels of csrc/v1_transform.hip --
+float32 fma chains per element, dT from float64 slab partials added in slab order, the
+regulariser's norm and mean one float64 chain each (include/pn2.h).
 
 The heads' FC layers (linear_bn_train, tuning key train_head=1): Linear + BatchNorm1d + ReLU of
 the FC tails, the translation heads' mean MLP and the T-Nets' tail under autograd, in train mode
@@ -295,6 +302,83 @@ def point_mlp_train(x, convs, bns, rows, pool=True, last_relu=True):
     return out if pool else out.view(B, N, -1)
 
 
+def point_mlp_frozen(x, convs, bns, rows, pool=True, last_relu=True):
+    """point_mlp_train's contract (rows, pool, last_relu) with eval-mode BatchNorm1d: the running
+    statistics normalise and are only read, num_batches_tracked stays (mlp_max_frozen's mode on
+    the v1 shared MLPs).  The recompute of the v1 modules' eval forward under autograd
+    (pn2/pointnet_utils._V1EvalGrad)."""
+    if rows:
+        B, N, C = x.shape
+        x0 = x.reshape(B * N, C)
+    else:
+        B, C, N = x.shape
+        x0 = x.permute(0, 2, 1).reshape(B * N, C)
+    if not x0.is_contiguous():
+        x0 = x0.contiguous()
+    cfg, params = [], []
+    n = len(convs)
+    for l, (conv, bn) in enumerate(zip(convs, bns)):
+        cfg.append(_bn_config(bn, last_relu or l < n - 1, True))
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    out = _MlpMaxTrain.apply(x0, N if pool else 0, tuple(cfg), *params)
+    return out if pool else out.view(B, N, -1)
+
+
+class _TransformPoints(torch.autograd.Function):
+    """y[b,n,:] = T[b] x[b,n,:] under autograd on the kernels of csrc/v1_transform.hip (forward,
+    dx and dT in the orders include/pn2.h states).  Saved for the backward: x and T, nothing
+    else."""
+
+    @staticmethod
+    def forward(ctx, x, T, rows):
+        ctx.rows = rows
+        ctx.save_for_backward(x, T)
+        return ops.transform_points_direct(x, T, rows)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, T = ctx.saved_tensors
+        dx, dT = ops.transform_points_backward_direct(dy, x, T, ctx.rows, ctx.needs_input_grad[0],
+                                                      ctx.needs_input_grad[1])
+        return dx, dT, None
+
+
+def transform_eligible(x, T):
+    """What transform_points covers: float32 device tensors and k <= 64."""
+    return (x.is_cuda and T.is_cuda and x.dtype == torch.float32 and T.dtype == torch.float32 and
+            1 <= T.shape[-1] <= ops.TRANSFORM_MAX_K)
+
+
+def transform_points(x, T, rows):
+    """The v1 networks' per-cloud transform under autograd: x rows [B, N, k] (rows=True;
+    ``torch.bmm(x, T.transpose(1, 2))``) or channel-first [B, k, N] (rows=False;
+    ``torch.bmm(T, x)``, pointnet_utils.py:108, 122), T [B, k, k] -> the transformed points in
+    x's layout.  Strided views are read in place."""
+    return _TransformPoints.apply(x, T, bool(rows))
+
+
+class _OrthoReg(torch.autograd.Function):
+    """feature_transform_reguliarzer (pointnet_utils.py:140-147) on pn2_orthogonality_forward_f32
+    / _backward_f32.  Saved for the backward: T and the per-cloud norms."""
+
+    @staticmethod
+    def forward(ctx, T):
+        loss, norm, _ = ops.orthogonality_forward_direct(T)
+        ctx.save_for_backward(T, norm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        T, norm = ctx.saved_tensors
+        return ops.orthogonality_backward_direct(T, norm, dloss.contiguous())
+
+
+def orthogonality_loss(T):
+    """mean_b ||T[b] T[b]^T - I||_F of T [B, k, k] (k <= 64, float32 on the device) under
+    autograd, every sum in a stated order (include/pn2.h)."""
+    return _OrthoReg.apply(T)
+
+
 class _FcBnTrain(torch.autograd.Function):
     """One FC layer of a head under autograd: Linear (+ BatchNorm1d with batch or frozen
     statistics) (+ ReLU) as pn2_fc_bn_forward_f32, its backward as pn2_fc_bn_backward_f32 plus
@@ -357,5 +441,5 @@ def linear_bn_train(x, fc, bn, relu=True):
     return _FcBnTrain.apply(x, _bn_config(bn, relu, not bn.training), fc.weight, fc.bias, bn.weight, bn.bias)
 
 
-__all__ = ["mlp_max_train", "mlp_max_frozen", "point_mlp_train", "group_train", "eligible",
-           "eligible_frozen", "linear_bn_train"]
+__all__ = ["mlp_max_train", "mlp_max_frozen", "point_mlp_train", "point_mlp_frozen", "group_train", "eligible",
+           "eligible_frozen", "linear_bn_train", "transform_points", "transform_eligible", "orthogonality_loss"]

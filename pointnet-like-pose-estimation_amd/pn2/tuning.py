@@ -82,6 +82,30 @@ Keys are the library's kernel-selection parameters (include/pn2.h ``pn2_tuning_s
                      kernels' route the slower one; the whole ClsSSG B=32 train step 5.746 /
                      5.746 ms.  The key buys the fixed order, not speed.
                      0 or 1; anything else is an error
+    v1_transform     0: the per-cloud transforms of the PointNet-v1 modules under autograd
+                     (PointNetEncoder's and PoseV1's two torch.bmm each) and
+                     feature_transform_reguliarzer are torch: library calls whose summation
+                     order -- bmm's backward sums over all N points of a cloud -- is the
+                     library's choice; 1: pn2.train.transform_points / orthogonality_loss
+                     (csrc/v1_transform.hip: pn2_transform_points_f32 / _backward_f32,
+                     pn2_orthogonality_forward_f32 / _backward_f32, every sum in a stated order,
+                     include/pn2.h) wherever a v1 module must be differentiable on float32 device
+                     tensors, in train mode and in eval under autograd.  CPU or non-float32
+                     tensors and k > 64 keep torch; the no_grad fused forward is untouched.
+                     With train_gemm=1, train_head=1 and train_loss=1 a pointnet_cls or pose
+                     train step then carries the guarantee stated for the PointNet++ heads
+                     (DESIGN.md §7).  0 or 1; anything else is an error
+    v1_eval_grad     0: a v1 module's eval-mode forward that must be differentiable runs the
+                     reference's Conv1d / BatchNorm1d formulation and saves every [B, C, N]
+                     activation; 1: pointnet_utils.mlp_mode answers "eval_grad" for float32
+                     device tensors, fp32 precision, layers train.eligible_frozen accepts and
+                     widths ops.sa_mlp_supported accepts: the shared MLPs run the fused
+                     inference kernels (the no_grad launches and bits) inside an autograd
+                     Function that saves the input only and recomputes the MLP on the
+                     frozen-statistics training kernels in its backward
+                     (pointnet_utils._V1EvalGrad, modelled on _SaEvalGrad).  Inside
+                     pn2.eval_autograd() the answer stays "torch".  0 or 1; anything else is an
+                     error
     pipe_profile     1: the pipelines (pn2.pipeline) whose launches carry >= 64 clouds
                      (fused groups, or B >= 64) capture and run their kernels under
                      PIPELINE_PROFILE -- the launch choices measured best beside each other's
@@ -118,10 +142,19 @@ HOST_DEFAULTS = {
 # host keys with a checked range (inclusive); the others take any integer
 HOST_RANGES = {"group_backward": (0, 1), "train_gemm": (0, 1), "train_head": (0, 1), "train_head_rows": (0, 1),
                "train_loss": (0, 1)}
+# The PointNet-v1 autograd routes' keys: host keys like the ones above in every respect (get,
+# override, PN2_TUNING), in a table of their own because tests/test_abi_loss.py pins
+# HOST_DEFAULTS to exactly the keys it had when train_loss was added.
+V1_DEFAULTS = {
+    "v1_transform": 0,
+    "v1_eval_grad": 0,
+}
+V1_RANGES = {"v1_transform": (0, 1), "v1_eval_grad": (0, 1)}
+_HOST_KEYS = {**HOST_DEFAULTS, **V1_DEFAULTS}
 
 
 def _check_host(key, value):
-    lo, hi = HOST_RANGES.get(key, (value, value))
+    lo, hi = HOST_RANGES.get(key, V1_RANGES.get(key, (value, value)))
     if not lo <= value <= hi:
         raise ValueError("pn2 tuning: %s=%r is outside [%d, %d]" % (key, value, lo, hi))
     return value
@@ -138,8 +171,8 @@ def _parse(text):
 
 
 _ENV = _parse(os.environ.get("PN2_TUNING", ""))
-_host = dict(HOST_DEFAULTS)
-_host.update({k: _check_host(k, v) for k, v in _ENV.items() if k in HOST_DEFAULTS})
+_host = dict(_HOST_KEYS)
+_host.update({k: _check_host(k, v) for k, v in _ENV.items() if k in _HOST_KEYS})
 
 
 # Kernel keys the pipelines set while they capture / run: the FPS block of 4
@@ -221,7 +254,7 @@ def _set_kernel(L, key, value):
 def apply_env(L):
     """Apply PN2_TUNING's kernel keys to the just-loaded library L (called by _lib.load)."""
     for k, v in _ENV.items():
-        if k not in HOST_DEFAULTS:
+        if k not in _HOST_KEYS:
             _set_kernel(L, k, v)
 
 
@@ -233,7 +266,7 @@ def override(**kw):
     saved = []
     try:
         for k, v in kw.items():
-            if k in HOST_DEFAULTS:
+            if k in _HOST_KEYS:
                 _check_host(k, v)
                 saved.append((k, _host[k], True))
                 _host[k] = v
