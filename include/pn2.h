@@ -621,6 +621,78 @@ int pn2_orthogonality_forward_f32(const float *T, int64_t ldt, int64_t B, int64_
 int pn2_orthogonality_backward_f32(const float *T, int64_t ldt, const float *norm, const float *dloss,
                                    int64_t B, int64_t k, float *dT, void *stream);
 
+/* ---- the optimizer step of a train step as one launch over every tensor (csrc/optim.hip).
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * Reference: every train script steps torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-08,
+ * weight_decay=args.decay_rate), or SGD(lr=0.01, momentum=0.9) under --optimizer SGD, after each
+ * batch, with StepLR(step_size=20, gamma=0.7) on top (train_classification.py:88-101, 128 and the
+ * other train_*.py alike).  pn2/optim.py is the host side.
+ *
+ * THE TABLES.  `tensors` is a DEVICE array of ntensors descriptors; `tensors_host` is the
+ * caller's HOST copy of the same array, read only by the argument check (the two must be equal:
+ * the kernel trusts the device copy's pointers and counts as it trusts any pointer argument).
+ * p, g, m, v are dense float32 arrays of n elements: the parameter, its gradient, and Adam's
+ * exp_avg and exp_avg_sq (for SGD m is the momentum_buffer, or NULL for a tensor without one,
+ * which then takes the plain update; v is not read).  `scalars` is the index of the tensor's
+ * scalar block.  `jobs` is a DEVICE array of njobs int32 pairs (tensor, chunk): workgroup w
+ * updates elements [chunk*C, min((chunk+1)*C, n)) of that tensor, C = pn2_optim_chunk() (2048, a
+ * constant of the build).  Every (tensor, chunk) with chunk*C < n appears exactly once, so njobs
+ * is the sum over the tensors of ceil(n / C); the order is free.  A pair that points outside the
+ * tables or past n is skipped by the kernel, never followed.
+ * 16-byte accesses are used for a whole chunk when the tensor's p, g, m and v base pointers are
+ * all 16-byte aligned, dword accesses otherwise (a partial last chunk, an unaligned base); both
+ * compute the same bits.  No LDS, no atomics, no cross-lane traffic: an element depends on its
+ * own p, g, m, v and its scalar block only.
+ *
+ * THE SCALARS LIVE IN DEVICE MEMORY, never in kernel arguments: `scalars` holds nblocks blocks of
+ * pn2_optim_scalars() (8) float32, which the host writes, stream-ordered, before each step.  A
+ * launch captured into a hipGraph therefore replays with the values written for THAT replay
+ * (the next step's bias corrections, a learning rate a scheduler changed).  The host computes
+ * them in float64 with the expressions below and rounds each to float32 once.
+ *   Adam block: [0] ss = -(lr / bc1), bc1 = 1 - beta1**step;  [1] bc2_sqrt = (1 - beta2**step)
+ *               ** 0.5;  [2] omb1 = 1 - beta1;  [3] beta2;  [4] omb2 = 1 - beta2;  [5] eps;
+ *               [6] wd = weight_decay;  [7] unused.
+ *   SGD block:  [0] lr;  [1] mu = momentum;  [2] omd = 1 - dampening;  [3] wd = weight_decay;
+ *               [4] first: nonzero on the step that creates the tensor's momentum_buffer;
+ *               [5..7] unused.
+ *
+ * THE ARITHMETIC RULE.  Every operation is ONE correctly rounded IEEE float32 operation
+ * (round to nearest even, subnormals kept), in this order, with no contraction:
+ *   pn2_adam_step_f32, per element:
+ *     g' = g + wd*p              only when wd != 0 (else g' = g)
+ *     m  = m + omb1*(g' - m)
+ *     v  = v*beta2;  v = v + (omb2*g')*g'
+ *     den = sqrt(v) / bc2_sqrt + eps
+ *     p  = p + ss*(m / den)
+ *   pn2_sgd_step_f32, per element (torch's _single_tensor_sgd order):
+ *     g' = g + wd*p              only when wd != 0
+ *     with a buffer:  buf = g' when first != 0 (the buffer is written, not read), else
+ *                     buf = buf*mu + omd*g';   then g' = buf
+ *     p  = p - lr*g'
+ *   Nesterov momentum, maximize and amsgrad are not built.  tests/optim_ref.py restates both
+ *   rules with numpy float32 operators and gives the kernels' bits.
+ *
+ * Errors, before any device call: PN2_EINVAL for a NULL table or scalar pointer, a NULL p or g
+ * (for Adam also m or v) in a descriptor, ntensors < 1 or nblocks < 1, a count n that is < 1 or
+ * >= 2^31, a scalar index outside [0, nblocks), njobs that does not match the tensors' chunk
+ * count; PN2_EUNSUPPORTED for more than 2^30 chunks. */
+typedef struct pn2_optim_tensor {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t n;
+    int64_t scalars;
+} pn2_optim_tensor;
+int64_t pn2_optim_chunk(void);
+int64_t pn2_optim_scalars(void);
+int pn2_adam_step_f32(const pn2_optim_tensor *tensors_host, const pn2_optim_tensor *tensors,
+                      int64_t ntensors, const int32_t *jobs, int64_t njobs, const float *scalars,
+                      int64_t nblocks, void *stream);
+int pn2_sgd_step_f32(const pn2_optim_tensor *tensors_host, const pn2_optim_tensor *tensors, int64_t ntensors,
+                     const int32_t *jobs, int64_t njobs, const float *scalars, int64_t nblocks,
+                     void *stream);
+
 /* One shared-MLP layer packed for the kernels: wt = W^T pair-interleaved, [cin_pad/2][cout][2]
  * (element (k, o) at ((k>>1)*cout + o)*2 + (k&1), zero rows past cin), alpha[cout], beta[cout]
  * such that layer(x) = relu(alpha * (W x) + beta): the eval-mode BatchNorm2d folded with the

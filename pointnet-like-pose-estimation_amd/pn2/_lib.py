@@ -39,6 +39,10 @@ class FpsSide(ctypes.Structure):
                 ("out_idx", _vp), ("out_pts", _vp), ("out_packed", _vp), ("pts_packed", _vp)]
 
 
+class OptimTensor(ctypes.Structure):
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _i64), ("scalars", _i64)]
+
+
 class SaSrc(ctypes.Structure):
     _fields_ = [
         ("mode", _int),
@@ -133,6 +137,10 @@ SIGNATURES = {
                                                  _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pn2_orthogonality_forward_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_orthogonality_backward_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "pn2_optim_chunk": (_i64, []),
+    "pn2_optim_scalars": (_i64, []),
+    "pn2_adam_step_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pn2_sgd_step_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pn2_layer_cin_pad": (_i64, [_i64]),
     "pn2_pack_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn2_layer_split_kblocks": (_i64, [_i64, _i64]),
