@@ -78,6 +78,10 @@
  *                                                            data_utils/ModelNetDataLoader.py:25-46;
  *                                                            point_collect/transformer.py:120-141;
  *                                                            data_build/Cube.py:102-123
+ *   pn2_clip_flags / pn2_radius_count_f64 / pn2_compact_rows / pn2_dbscan_labels
+ *                          the capture scripts' clip_distance, delet_outlier_radius, cluster_point
+ *                                                            point_collect/collect.py:30-102;
+ *                                                            camera_test/camera.py:131
  */
 #ifndef PN2_H
 #define PN2_H
@@ -224,6 +228,73 @@ int pn2_fps_points(const void *pts, int dtype, int64_t B, const int64_t *offsets
                    const int64_t *starts, int64_t total_rows, int64_t max_n, int64_t C, int64_t ld,
                    int64_t S, int64_t *out_idx, void *out_pts, void *workspace,
                    int64_t workspace_bytes, void *stream);
+
+/* ---- camera-cloud front end: clip_distance, delet_outlier_radius, cluster_point
+ * (point_collect/collect.py:30-102 and its copy colledt_data_structure/collect.py;
+ * camera_test/camera.py:131; csrc/collect.hip).
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * A cloud is pts [N][ld] rows of `dtype` elements (PN2_DTYPE_F32 / PN2_DTYPE_F64), 3 <= C <= 64,
+ * ld >= C, N <= pn2_collect_max_points() = 2^20 (above: PN2_EUNSUPPORTED; DESIGN.md 4.4 has the
+ * arithmetic).  Rows are carried whole; distances use columns 0..2.  Every result is a selection
+ * of input rows or an integer, so parity with the rules below is bit for bit.
+ *  1 Clip.  Row i is kept iff lo <= p[i][axis] <= hi, compared in float64 (a float32 value widened),
+ *    in input order; a NaN fails both tests.
+ *  2 Neighbour.  d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in float64 (float32 inputs widened first),
+ *    dx = x_i - x_j, every operation rounded once, no contraction.  j is a neighbour of i iff
+ *    d2 < r*r, r*r one float64 product.  Every finite point is its own neighbour, and so is each
+ *    of its duplicates; a point with a NaN coordinate has no neighbour.
+ *  3 Radius filter.  Row i is kept iff its neighbour count, itself included, is > nb_points;
+ *    input order.
+ *  4 DBSCAN labels.  A point is core iff its neighbour count is >= min_points.  Clusters are the
+ *    connected components of the core points under the neighbour relation, numbered 0, 1, ... in
+ *    ascending order of their smallest core index.  A non-core point with a core neighbour takes
+ *    the smallest label among its core neighbours; every other point is -1.
+ *  5 cluster_point: the rows of cluster l in ascending index order, each cluster sampled to the
+ *    smallest cluster's size by pn2_fps_points (pn2/collect.py draws the starts).
+ *
+ * pn2_clip_flags        flags[i] = 1 / 0 by rule 1 (int32 [N], device); 0 <= axis < C.
+ * pn2_radius_count_f64  counts[i] = neighbours of i by rule 2 with r = radius (int32 [N]).  Tiled
+ *                       brute force: N * N pairs, no atomics, two runs give the same bits.
+ * pn2_compact_rows      order-preserving bucket sort of rows by keys[i] (int32 [N], device):
+ *                         PN2_COMPACT_FLAG_GT  one bucket (L == 1): the rows with keys[i] > thresh
+ *                         PN2_COMPACT_FLAG_LE  one bucket (L == 1): the rows with keys[i] <= thresh
+ *                         PN2_COMPACT_LABEL    L buckets: row i to bucket keys[i] when 0 <= keys[i]
+ *                                              < L; negative keys are dropped, a key >= L is
+ *                                              dropped and raises PN2_DEVERR_INDEX
+ *                       out_rows [N][C] `dtype` receives the kept rows (only the first offsets[L] are
+ *                       written), bucket after bucket, each in ascending input index; out_src (int32
+ *                       [N], or NULL) their input indices; offsets [L+1] int64 (device): bucket b is
+ *                       the output rows offsets[b] .. offsets[b+1]-1 -- the table pn2_fps_points
+ *                       takes.  Rows move as 16-byte pieces when C and ld are whole multiples of
+ *                       16 bytes and both base pointers are 16-byte aligned, else element by element.
+ *                       Workspace: pn2_compact_rows_workspace_bytes(N, L) bytes, 16-byte aligned
+ *                       (-1: bad arguments, or ceil(N / 256) * L above 2^26 table entries, for
+ *                       which the entry returns PN2_EUNSUPPORTED).
+ * pn2_dbscan_labels     labels [N] int32 by rule 4 from counts [N] (pn2_radius_count_f64 with
+ *                       r = eps) and *nclusters (int64, device) = the number of clusters.  A
+ *                       lock-free union-find over the core-core neighbour pairs (32-bit parents, the
+ *                       larger root always linked under the smaller by compare-and-swap), then a
+ *                       flatten pass, a prefix sum over "is root" and one pass for the non-core
+ *                       points.  No host read; two runs give the same bits.  Workspace:
+ *                       pn2_dbscan_labels_workspace_bytes(N) bytes, 16-byte aligned.
+ * N == 0: PN2_OK, nothing is written, no launch. */
+#define PN2_COMPACT_FLAG_GT 0
+#define PN2_COMPACT_LABEL 1
+#define PN2_COMPACT_FLAG_LE 2
+int64_t pn2_collect_max_points(void);
+int pn2_clip_flags(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld, int64_t axis,
+                   double lo, double hi, int32_t *flags, void *stream);
+int pn2_radius_count_f64(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld, double radius,
+                         int32_t *counts, void *stream);
+int64_t pn2_compact_rows_workspace_bytes(int64_t N, int64_t L);
+int pn2_compact_rows(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld,
+                     const int32_t *keys, int mode, int64_t thresh, int64_t L, void *out_rows,
+                     int32_t *out_src, int64_t *offsets, void *workspace, int64_t workspace_bytes,
+                     void *stream);
+int64_t pn2_dbscan_labels_workspace_bytes(int64_t N);
+int pn2_dbscan_labels(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld, double eps,
+                      int64_t min_points, const int32_t *counts, int32_t *labels, int64_t *nclusters,
+                      void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Pack a [B,N,C] strided view into [B,N,cp] with its ssq (see above).  C <= 64, as for the
  * ball query and square_distance below (else PN2_EUNSUPPORTED). */

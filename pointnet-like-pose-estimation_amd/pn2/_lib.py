@@ -74,6 +74,7 @@ DEVERR_NO_NEIGHBOUR = 1
 DEVERR_INDEX = 2
 DTYPE_F32 = 0
 DTYPE_F64 = 1
+COMPACT_FLAG_GT, COMPACT_LABEL, COMPACT_FLAG_LE = 0, 1, 2
 INDEX_I64 = 0
 INDEX_I32 = 1
 LOSS_NLL, LOSS_MSE, LOSS_L1, LOSS_BCE = 0, 1, 2, 3
@@ -97,6 +98,14 @@ SIGNATURES = {
     "pn2_fps_points_workspace_bytes": (_i64, [_int, _i64, _i64]),
     "pn2_fps_points": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64,
                               _vp]),
+    "pn2_collect_max_points": (_i64, []),
+    "pn2_clip_flags": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _dbl, _dbl, _vp, _vp]),
+    "pn2_radius_count_f64": (_int, [_vp, _int, _i64, _i64, _i64, _dbl, _vp, _vp]),
+    "pn2_compact_rows_workspace_bytes": (_i64, [_i64, _i64]),
+    "pn2_compact_rows": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _i64,
+                                _vp]),
+    "pn2_dbscan_labels_workspace_bytes": (_i64, [_i64]),
+    "pn2_dbscan_labels": (_int, [_vp, _int, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pn2_pack_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pn2_ball_query_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
     "pn2_ball_query_cnt_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp]),

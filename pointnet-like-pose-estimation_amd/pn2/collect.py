@@ -1,0 +1,170 @@
+"""The camera-cloud front end of the reference's capture scripts on the GPU
+(point_collect/collect.py:30-102, its copy colledt_data_structure/collect.py, and
+camera_test/camera.py:131): a frame's cloud is cut to a depth range (clip_distance), cleaned of
+sparse points (delet_outlier_radius) and split into objects that are FPS-sampled to a common size
+(cluster_point).  The reference runs them as numpy masks and Open3D kd-tree calls on the host; here
+they are the kernels of csrc/collect.hip plus the existing numpy-rule FPS (csrc/fps_points.hip),
+by the rules include/pn2.h states.  Names, misspellings included, defaults and return shapes are
+the reference's; cluster_point's `visualize` flag is not carried.
+
+Input is [N, C], 3 <= C <= 64, float64 or float32: a numpy array (the result is a numpy array) or a
+torch tensor (the result is a tensor on the device it ran on), with the optional device= of
+pn2.provider.farthest_point_sample_batch.  Rows are carried whole; distances use columns 0..2.
+There is no CPU path."""
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _stream
+from .provider import _DOWNSAMPLE_DTYPES, _pick_device
+
+
+def _cloud(who, point_cloud, device):
+    """-> (rows on the device with unit column stride, whether the input was a host array)"""
+    host = not isinstance(point_cloud, torch.Tensor)
+    if host:
+        a = np.ascontiguousarray(np.asarray(point_cloud))
+        point_cloud = torch.from_numpy(a if a.flags.writeable else a.copy())
+    t = point_cloud
+    if t.dim() != 2:
+        raise ValueError("pn2.collect.%s: point_cloud must be [N, C], got shape %s" % (who, tuple(t.shape)))
+    if t.dtype not in _DOWNSAMPLE_DTYPES:
+        raise TypeError("pn2.collect.%s: point_cloud must be float64 or float32, got %s" % (who, t.dtype))
+    N, C = t.shape
+    if C < 3 or C > 64:
+        raise ValueError("pn2.collect.%s: needs 3 <= C <= 64, got C = %d" % (who, C))
+    limit = _lib.load().pn2_collect_max_points()
+    if N > limit:
+        raise ValueError("pn2.collect.%s: %d points, above the %d the kernels take" % (who, N, limit))
+    dev = _pick_device(who, t, device)
+    t = t.to(dev, non_blocking=True)
+    if N and (t.stride(1) != 1 or (N > 1 and t.stride(0) < C)):
+        t = t.contiguous()
+    return t, host
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _result(t, host):
+    return t.cpu().numpy() if host else t
+
+
+def _compact(t, keys, mode, thresh=0, L=1):
+    """pn2_compact_rows -> (rows [N, C] of which the first offsets[L] are written, offsets [L+1])"""
+    N, C = t.shape
+    lib = _lib.load()
+    with torch.cuda.device(t.device):
+        out = torch.empty(N, C, dtype=t.dtype, device=t.device)
+        offsets = torch.zeros(L + 1, dtype=torch.int64, device=t.device)
+        need = lib.pn2_compact_rows_workspace_bytes(N, L)
+        if need < 0:
+            raise ValueError("pn2.collect: %d rows in %d buckets are more than one compaction takes" % (N, L))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
+        _lib.check(lib.pn2_compact_rows(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), keys.data_ptr(),
+                                        mode, thresh, L, out.data_ptr(), None, offsets.data_ptr(), ws.data_ptr(),
+                                        need, _stream(out)), "pn2_compact_rows")
+    return out, offsets
+
+
+def _counts(t, radius):
+    N, C = t.shape
+    with torch.cuda.device(t.device):
+        counts = torch.empty(N, dtype=torch.int32, device=t.device)
+        _lib.check(_lib.load().pn2_radius_count_f64(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t),
+                                                    float(radius), counts.data_ptr(), _stream(counts)),
+                   "pn2_radius_count_f64")
+    return counts
+
+
+def _labels(t, eps, min_points):
+    """-> (labels int32 [N], number of clusters as a device int64 [1]); no host read"""
+    N, C = t.shape
+    lib = _lib.load()
+    counts = _counts(t, eps)
+    with torch.cuda.device(t.device):
+        labels = torch.empty(N, dtype=torch.int32, device=t.device)
+        ncl = torch.zeros(1, dtype=torch.int64, device=t.device)
+        need = lib.pn2_dbscan_labels_workspace_bytes(N)
+        ws = torch.empty(need, dtype=torch.uint8, device=t.device)
+        _lib.check(lib.pn2_dbscan_labels(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), float(eps),
+                                         int(min_points), counts.data_ptr(), labels.data_ptr(), ncl.data_ptr(),
+                                         ws.data_ptr(), need, _stream(labels)), "pn2_dbscan_labels")
+    return labels, ncl
+
+
+def _bound(x, dtype):
+    """A bound as numpy's comparison sees it: a Python number takes the cloud's dtype, a numpy
+    value promotes with it.  Either way it is exact in float64, where the kernel compares."""
+    b = np.asarray(x)
+    np_dtype = np.float32 if dtype == torch.float32 else np.float64
+    b = b.astype(np_dtype if type(x) in (int, float) else np.result_type(np_dtype, b.dtype))
+    return float(b)
+
+
+def clip_distance(point_cloud, dis=[0, 2], axis=2, device=None):
+    """Keep the rows with dis[0] <= point_cloud[:, axis] <= dis[1], in input order."""
+    t, host = _cloud("clip_distance", point_cloud, device)
+    N, C = t.shape
+    axis = int(axis)
+    if not -C <= axis < C:
+        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (axis, C))
+    if N == 0:
+        return _result(t, host)
+    with torch.cuda.device(t.device):
+        flags = torch.empty(N, dtype=torch.int32, device=t.device)
+        _lib.check(_lib.load().pn2_clip_flags(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), axis % C,
+                                              _bound(dis[0], t.dtype), _bound(dis[1], t.dtype), flags.data_ptr(),
+                                              _stream(flags)), "pn2_clip_flags")
+    out, offsets = _compact(t, flags, _lib.COMPACT_FLAG_GT)
+    return _result(out[:int(offsets[1].item())], host)  # the one host read: the result's length
+
+
+def delet_outlier_radius(point_cloud, nb_points=200, radius=0.05, device=None):
+    """Keep the rows with more than nb_points points (themselves included) within radius."""
+    t, host = _cloud("delet_outlier_radius", point_cloud, device)
+    if t.shape[0] == 0:
+        return _result(t, host)
+    out, offsets = _compact(t, _counts(t, radius), _lib.COMPACT_FLAG_GT, int(nb_points))
+    return _result(out[:int(offsets[1].item())], host)
+
+
+def dbscan_labels(point_cloud, eps, min_points, device=None):
+    """The labels cluster_point uses (include/pn2.h rule 4): int32 [N], -1 for noise."""
+    t, host = _cloud("dbscan_labels", point_cloud, device)
+    if t.shape[0] == 0:
+        return _result(torch.empty(0, dtype=torch.int32, device=t.device), host)
+    return _result(_labels(t, eps, min_points)[0], host)
+
+
+def cluster_point(point_cloud, eps=0.03, min_points=500, device=None):
+    """DBSCAN, then every cluster FPS-sampled to the smallest cluster's size: [L, min_number, C]
+    float64, or None (and the reference's printed line) when no cluster is found.  One
+    np.random.randint(0, n_i) is drawn per cluster, in label order, from numpy's global
+    generator.  The host reads the number of clusters and their sizes; the rest stays on the
+    device."""
+    from .provider import _fps_points_launch
+    t, host = _cloud("cluster_point", point_cloud, device)
+    N, C = t.shape
+    L = 0
+    if N:
+        labels, ncl = _labels(t, eps, min_points)
+        L = int(ncl.item())
+    if L == 0:
+        print('Null point')
+        return None
+    rows, offsets = _compact(t, labels, _lib.COMPACT_LABEL, 0, L)
+    offsets = offsets.cpu().numpy()
+    sizes = np.diff(offsets).tolist()
+    starts = np.zeros(L, dtype=np.int64)
+    for i, n in enumerate(sizes):
+        if n == 1:  # the reference's squeeze() leaves a [C] vector that its FPS cannot unpack
+            raise ValueError("not enough values to unpack (expected 2, got 1)")
+        starts[i] = np.random.randint(0, n)
+    min_number = min(sizes)
+    _, out = _fps_points_launch(rows, C, C, offsets, starts, int(offsets[L]), max(sizes), min_number)
+    return _result(out.double(), host)
+
+
+__all__ = ["clip_distance", "delet_outlier_radius", "cluster_point", "dbscan_labels"]
