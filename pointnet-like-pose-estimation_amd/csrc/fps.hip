@@ -48,7 +48,9 @@ __global__ __launch_bounds__(NT) void fps2_kernel(const Fps2Args G) {
 // cloud's N words fit (DL), else in the caller's workspace (one word per point) -- and keeps
 // the 64-bit key (distance bits : ~index), whose maximum is torch.max's first index among the
 // maxima.  Wave max by shuffles, one LDS slot per wave (double-buffered by parity), ONE
-// barrier, every thread reduces the NW slots.  The centroid's coordinates are re-read from
+// barrier, every thread reduces the NW slots (the exchange of fps_points.hip's wg_argmax, kept
+// in this packed form: as pairs the workspace variant measured 0.5 % slower).
+// The centroid's coordinates are re-read from
 // the input (one broadcast load).  Indices go straight to out_idx; the output pass reads them
 // back with sc1 loads (stores of other waves of this workgroup).
 // Point dimensions past the register-resident kMaxC (16 < C <= kMaxCWide) always take this
@@ -68,16 +70,19 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 }
 
 template <int CM, bool FIXED, bool DL>
-__global__ __launch_bounds__(fps_stream_threads<CM>()) void fps_stream_kernel(
-    const float *__restrict__ pts, int N, int Crt, int64_t sb, int64_t sn, int64_t sc, int kind,
-    const FpsStart start, int S, int64_t *__restrict__ out_idx, float *__restrict__ out_pts,
-    float *__restrict__ out_packed, float *__restrict__ pts_packed, int cp, unsigned *__restrict__ dist_ws) {
+__global__ __launch_bounds__(fps_stream_threads<CM>()) void fps_stream_kernel(const FpsArgs F,
+                                                                              unsigned *__restrict__ dist_ws) {
     constexpr int NT = fps_stream_threads<CM>(), NW = NT / 64;
+    // always raised: the tuning key fps_prio (F.prio) governs only the resident kernels
     __builtin_amdgcn_s_setprio(PN2_FPS_PRIO);
-    const int C = FIXED ? CM : Crt;
+    const int N = F.N, C = FIXED ? CM : F.C, kind = F.kind, S = F.S, cp = F.cp;
+    const int64_t sn = F.sn, sc = F.sc;
+    float *__restrict__ out_pts = F.out_pts;
+    float *__restrict__ out_packed = F.out_packed;
+    float *__restrict__ pts_packed = F.pts_packed;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
-    const float *P = pts + (int64_t)b * sb;
+    const float *__restrict__ P = F.pts + (int64_t)b * F.sb;
     extern __shared__ __attribute__((aligned(16))) unsigned long long ssm[];
     unsigned long long *slots = ssm;                               // [2][NW]
     unsigned *dist = DL ? reinterpret_cast<unsigned *>(ssm + 2 * NW)  // [N]
@@ -101,11 +106,11 @@ __global__ __launch_bounds__(fps_stream_threads<CM>()) void fps_stream_kernel(
             for (int k = C + 1; k < cp; ++k) dst[k] = 0.f;
         }
     }
-    int far = fps_start(start, b);
+    int far = fps_start(F.start, b);
     float c[CM];
     point(far, c);
     __syncthreads();
-    int64_t *oi = out_idx + (int64_t)b * S;
+    int64_t *__restrict__ oi = F.out_idx + (int64_t)b * S;
     for (int i = 0;; ++i) {
         if (tid == 0) oi[i] = far;
         if (i == S - 1) break;
@@ -196,10 +201,11 @@ using namespace pn2;
 
 extern "C" int64_t pn2_packed_stride(int64_t C) { return ((C + 1 + 3) / 4) * 4; }
 
-// the FpsArgs of a launch (or side job) over points pts[b*sb + n*sn + c*sc]
-FpsArgs pn2::fps_args(const float *pts, int64_t N, int64_t C, int64_t sb, int64_t sn, int64_t sc,
-                 const FpsStart &start, int64_t S, int64_t *out_idx, float *out_pts, float *out_packed,
-                 float *pts_packed) {
+// the FpsArgs of a launch (or side job) over points pts[b*sb + n*sn + c*sc], starts from the
+// device array start_dev (null: carried in the arguments, fps_host_starts)
+static FpsArgs fps_args(const float *pts, int64_t N, int64_t C, int64_t sb, int64_t sn, int64_t sc,
+                        const int64_t *start_dev, int64_t S, int64_t *out_idx, float *out_pts,
+                        float *out_packed, float *pts_packed) {
     FpsArgs F;
     F.pts = pts;
     F.N = (int)N;
@@ -215,15 +221,48 @@ FpsArgs pn2::fps_args(const float *pts, int64_t N, int64_t C, int64_t sb, int64_
     F.pts_packed = pts_packed;
     F.cp = (int)pn2_packed_stride(C);
     F.prio = tuning().fps_prio ? 1 : 0;
-    F.start = start;
+    F.start.dev = start_dev;
     return F;
 }
 
+// One FPS call, built once by its entry point: the kernels' argument block for clouds 0 .. B-1
+// and the streamed kernel's workspace (one word per point; null where none is needed)
+struct FpsCall {
+    FpsArgs F;
+    int64_t B;
+    unsigned *ws;
+};
+
+// start[0 .. B) of a host array inside [0, N), else who's error; then into the argument block
+static int fps_host_starts_check(const char *who, const int64_t *start, int64_t B, int64_t N) {
+    for (int64_t b = 0; b < B; ++b)
+        PN2_REQUIRE(start[b] >= 0 && start[b] < N, "%s: start[%lld] = %lld outside [0, %lld)", who,
+                    (long long)b, (long long)start[b], (long long)N);
+    return PN2_OK;
+}
+static void fps_host_starts(FpsStart &fs, const int64_t *start, int64_t B) {
+    fs.dev = nullptr;
+    for (int64_t b = 0; b < B; ++b) fs.v[b] = (int)start[b];
+}
+
+// the call over its clouds b0 .. B-1; an optional output or workspace that is absent stays absent
+static FpsCall fps_advance(FpsCall c, int64_t b0) {
+    const auto off = [](auto *p, int64_t n) { return p ? p + n : nullptr; };
+    FpsArgs &F = c.F;
+    F.pts += b0 * F.sb;
+    F.out_idx += b0 * F.S;
+    F.out_pts = off(F.out_pts, b0 * F.S * F.C);
+    F.out_packed = off(F.out_packed, b0 * F.S * F.cp);
+    F.pts_packed = off(F.pts_packed, b0 * F.N * F.cp);
+    c.ws = off(c.ws, b0 * F.N);
+    c.B -= b0;
+    return c;
+}
+
 template <int NT, int PPT, int CM, bool FIXED, int CR = CM>
-static int launch_fps(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
-                      int64_t sc, const FpsStart &start, int64_t S, int64_t *out_idx,
-                      float *out_pts, float *out_packed, float *pts_packed, hipStream_t st) {
-    const FpsArgs F = fps_args(pts, N, C, sb, sn, sc, start, S, out_idx, out_pts, out_packed, pts_packed);
+static int launch_fps(const FpsCall &c, hipStream_t st) {
+    const FpsArgs &F = c.F;
+    const int64_t B = c.B, N = F.N, S = F.S;
     const size_t head = fps_block_lds(NT, CM, true, 0, S);
     const size_t cloud = fps_block_lds(NT, CM, true, N, S) - head;
     const bool ldsc = CR == CM && cloud <= (size_t)kFpsLdsCloud && head + cloud <= (size_t)160 * 1024;
@@ -246,20 +285,18 @@ static int launch_fps(const float *pts, int64_t B, int64_t N, int64_t C, int64_t
 // Block shape per cloud size.  Tuning fps_threads / fps_ppt force one of the compiled shapes
 // (tuning experiments only).
 template <int CM, bool FIXED, int CAP>
-static int dispatch_fps(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
-                        int64_t sc, const FpsStart &start, int64_t S, int64_t *out_idx,
-                        float *out_pts, float *out_packed, float *pts_packed, hipStream_t st) {
-#define A pts, B, N, C, sb, sn, sc, start, S, out_idx, out_pts, out_packed, pts_packed, st
+static int dispatch_fps(const FpsCall &c, hipStream_t st) {
+    const int64_t N = c.F.N;
     const int64_t fnt = tuning().fps_threads, fppt = tuning().fps_ppt;
 #define PN2_FPS_TRY(nt, ppt) \
-    if (fnt == nt && fppt == ppt && N <= (int64_t)nt * ppt) return launch_fps<nt, ppt, CM, FIXED>(A);
+    if (fnt == nt && fppt == ppt && N <= (int64_t)nt * ppt) return launch_fps<nt, ppt, CM, FIXED>(c, st);
     PN2_FPS_TRY(64, 8) PN2_FPS_TRY(64, 16) PN2_FPS_TRY(128, 4) PN2_FPS_TRY(128, 8) PN2_FPS_TRY(256, 2)
     PN2_FPS_TRY(256, 4) PN2_FPS_TRY(512, 2) PN2_FPS_TRY(1024, 1) PN2_FPS_TRY(512, 4) PN2_FPS_TRY(1024, 2)
     if constexpr (CM == 3) {
         PN2_FPS_TRY(512, 16) PN2_FPS_TRY(512, 32) PN2_FPS_TRY(256, 32) PN2_FPS_TRY(1024, 8)
     }
 #undef PN2_FPS_TRY
-    if (N <= 256) return launch_fps<64, 4, CM, FIXED>(A);
+    if (N <= 256) return launch_fps<64, 4, CM, FIXED>(c, st);
     // measured on MI355X (tools/bench_fps.py): two points per lane and 4-16 waves win until
     // the per-wave register set grows; past 2048 points the block is capped at 1024 threads.
     // Up to 1024 points (tuning fps_mid): alone on the chip 8 waves of 2 points are fastest
@@ -268,21 +305,20 @@ static int dispatch_fps(const float *pts, int64_t B, int64_t N, int64_t C, int64
     // points read ~2 % better (K = 100, tools/gpu_r04ab.sh), so pn2/pipeline.py selects that
     // for its geometry
     if (N <= 1024) {
-        if (tuning().fps_mid == 256) return launch_fps<256, 4, CM, FIXED>(A);
-        return launch_fps<512, 2, CM, FIXED>(A);
+        if (tuning().fps_mid == 256) return launch_fps<256, 4, CM, FIXED>(c, st);
+        return launch_fps<512, 2, CM, FIXED>(c, st);
     }
-    if (N <= 2048) return launch_fps<1024, 2, CM, FIXED>(A);
-    if (N <= 4096) return launch_fps<1024, 4, CM, FIXED>(A);
+    if (N <= 2048) return launch_fps<1024, 2, CM, FIXED>(c, st);
+    if (N <= 4096) return launch_fps<1024, 4, CM, FIXED>(c, st);
     if constexpr (CAP >= 8192)
-        if (N <= 8192) return launch_fps<1024, 8, CM, FIXED>(A);
+        if (N <= 8192) return launch_fps<1024, 8, CM, FIXED>(c, st);
     if constexpr (CAP >= 16384)
-        if (N <= 16384) return launch_fps<1024, 16, CM, FIXED>(A);
+        if (N <= 16384) return launch_fps<1024, 16, CM, FIXED>(c, st);
     // past the register-resident caps: xyz in registers, the other channels re-read from the
     // input each iteration when they are not constant (the pose heads' one-hot clouds -- e.g.
     // the 10000-point camera scans -- never read them)
     if constexpr (CM > 3)
-        if (N <= 16384) return launch_fps<1024, 16, CM, FIXED, 3>(A);
-#undef A
+        if (N <= 16384) return launch_fps<1024, 16, CM, FIXED, 3>(c, st);
     return set_error(PN2_EUNSUPPORTED, "pn2_fps_f32: N=%lld: no register-resident shape", (long long)N);
 }
 
@@ -292,24 +328,19 @@ static size_t fps_stream_lds(int64_t N, int nt = kFpsStreamT) { return (size_t)2
 static bool fps_stream_dl(int64_t N, int nt = kFpsStreamT) { return fps_stream_lds(N, nt) <= (size_t)160 * 1024; }
 
 template <int CM, bool FIXED>
-static int launch_fps_stream(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
-                             int64_t sc, const FpsStart &start, int64_t S, int64_t *out_idx, float *out_pts,
-                             float *out_packed, float *pts_packed, unsigned *ws, hipStream_t st) {
-    const int kind = layout_kind(sn, sc);
-    const int cp = (int)pn2_packed_stride(C);
+static int launch_fps_stream(const FpsCall &c, hipStream_t st) {
     constexpr int NT = fps_stream_threads<CM>();
+    const int64_t N = c.F.N;
     if (fps_stream_dl(N, NT)) {
         static const hipError_t attr = hipFuncSetAttribute(
             reinterpret_cast<const void *>(&fps_stream_kernel<CM, FIXED, true>),
             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         PN2_REQUIRE(attr == hipSuccess, "pn2_fps_f32: LDS attribute: %s", hipGetErrorString(attr));
-        hipLaunchKernelGGL((fps_stream_kernel<CM, FIXED, true>), dim3((unsigned)B), dim3(NT),
-                           fps_stream_lds(N, NT), st, pts, (int)N, (int)C, sb, sn, sc, kind, start, (int)S, out_idx,
-                           out_pts, out_packed, pts_packed, cp, nullptr);
+        hipLaunchKernelGGL((fps_stream_kernel<CM, FIXED, true>), dim3((unsigned)c.B), dim3(NT),
+                           fps_stream_lds(N, NT), st, c.F, nullptr);
     } else {
-        hipLaunchKernelGGL((fps_stream_kernel<CM, FIXED, false>), dim3((unsigned)B), dim3(NT),
-                           fps_stream_lds(0, NT), st, pts, (int)N, (int)C, sb, sn, sc, kind, start, (int)S, out_idx,
-                           out_pts, out_packed, pts_packed, cp, ws);
+        hipLaunchKernelGGL((fps_stream_kernel<CM, FIXED, false>), dim3((unsigned)c.B), dim3(NT),
+                           fps_stream_lds(0, NT), st, c.F, c.ws);
     }
     PN2_LAUNCH_CHECK("fps_stream_kernel");
     return PN2_OK;
@@ -336,21 +367,17 @@ static int fps_check(const float *pts, const int64_t *start, int64_t *out_idx, i
     return PN2_OK;
 }
 
-static int fps_run(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn, int64_t sc,
-                   const FpsStart &start, int64_t S, int64_t *out_idx, float *out_pts, float *out_packed,
-                   float *pts_packed, void *workspace, hipStream_t st) {
-#define A pts, B, N, C, sb, sn, sc, start, S, out_idx, out_pts, out_packed, pts_packed
-    if (C > kMaxC) return launch_fps_stream<kMaxCWide, false>(A, static_cast<unsigned *>(workspace), st);
-    if (!fps_resident(N, S)) {
-        unsigned *ws = static_cast<unsigned *>(workspace);
-        if (C == 3) return launch_fps_stream<3, true>(A, ws, st);
-        if (C == 10) return launch_fps_stream<10, true>(A, ws, st);
-        return launch_fps_stream<kMaxC, false>(A, ws, st);
+static int fps_run(const FpsCall &c, hipStream_t st) {
+    const int C = c.F.C;
+    if (C > kMaxC) return launch_fps_stream<kMaxCWide, false>(c, st);
+    if (!fps_resident(c.F.N, c.F.S)) {
+        if (C == 3) return launch_fps_stream<3, true>(c, st);
+        if (C == 10) return launch_fps_stream<10, true>(c, st);
+        return launch_fps_stream<kMaxC, false>(c, st);
     }
-    if (C == 3) return dispatch_fps<3, true, 16384>(A, st);
-    if (C == 10) return dispatch_fps<10, true, 8192>(A, st);
-    return dispatch_fps<kMaxC, false, 4096>(A, st);
-#undef A
+    if (C == 3) return dispatch_fps<3, true, 16384>(c, st);
+    if (C == 10) return dispatch_fps<10, true, 8192>(c, st);
+    return dispatch_fps<kMaxC, false, 4096>(c, st);
 }
 
 extern "C" int pn2_fps_ws_f32(const float *pts, int64_t B, int64_t N, int64_t C, int64_t sb, int64_t sn,
@@ -359,10 +386,9 @@ extern "C" int pn2_fps_ws_f32(const float *pts, int64_t B, int64_t N, int64_t C,
                               void *stream) {
     const int rc = fps_check(pts, start, out_idx, B, N, C, S, workspace, workspace_bytes);
     if (rc != PN2_OK || B == 0) return rc;
-    FpsStart fs;
-    fs.dev = start;
-    return fps_run(pts, B, N, C, sb, sn, sc, fs, S, out_idx, out_pts, out_packed, pts_packed, workspace,
-                   as_stream(stream));
+    const FpsCall c = {fps_args(pts, N, C, sb, sn, sc, start, S, out_idx, out_pts, out_packed, pts_packed), B,
+                       static_cast<unsigned *>(workspace)};
+    return fps_run(c, as_stream(stream));
 }
 
 // start in host memory, read during the call (the caller may reuse it on return): carried in
@@ -374,20 +400,14 @@ extern "C" int pn2_fps_host_ws_f32(const float *pts, int64_t B, int64_t N, int64
                                    int64_t workspace_bytes, void *stream) {
     int rc = fps_check(pts, start_host, out_idx, B, N, C, S, workspace, workspace_bytes);
     if (rc != PN2_OK || B == 0) return rc;
-    for (int64_t b = 0; b < B; ++b)
-        PN2_REQUIRE(start_host[b] >= 0 && start_host[b] < N, "pn2_fps_f32: start[%lld] = %lld outside [0, %lld)",
-                    (long long)b, (long long)start_host[b], (long long)N);
-    const int cp = (int)pn2_packed_stride(C);
-    hipStream_t st = as_stream(stream);
-    FpsStart fs;
-    fs.dev = nullptr;
+    if ((rc = fps_host_starts_check("pn2_fps_f32", start_host, B, N)) != PN2_OK) return rc;
+    const FpsCall c = {fps_args(pts, N, C, sb, sn, sc, nullptr, S, out_idx, out_pts, out_packed, pts_packed), B,
+                       static_cast<unsigned *>(workspace)};
     for (int64_t b0 = 0; b0 < B; b0 += kFpsArgStarts) {
-        const int64_t nb = std::min<int64_t>(kFpsArgStarts, B - b0);
-        for (int64_t j = 0; j < nb; ++j) fs.v[j] = (int)start_host[b0 + j];
-        rc = fps_run(pts + b0 * sb, nb, N, C, sb, sn, sc, fs, S, out_idx + b0 * S, out_pts ? out_pts + b0 * S * C : nullptr,
-                     out_packed ? out_packed + b0 * S * cp : nullptr, pts_packed ? pts_packed + b0 * N * cp : nullptr,
-                     workspace ? static_cast<unsigned *>(workspace) + b0 * N : nullptr, st);
-        if (rc != PN2_OK) return rc;
+        FpsCall k = fps_advance(c, b0);
+        k.B = std::min<int64_t>(kFpsArgStarts, k.B);
+        fps_host_starts(k.F.start, start_host + b0, k.B);
+        if ((rc = fps_run(k, as_stream(stream))) != PN2_OK) return rc;
     }
     return PN2_OK;
 }
@@ -425,10 +445,8 @@ extern "C" int pn2_fps2_f32(const float *pts, int64_t B, int64_t N, int64_t C, i
                          "(pn2_fps2_eligible): run two pn2_fps_f32 launches",
                          (long long)N, (long long)C, (long long)S1, (long long)S2);
     if (B == 0) return PN2_OK;
-    FpsStart fs;
-    fs.dev = start1;
     Fps2Args G;
-    G.l1 = fps_args(pts, N, C, sb, sn, sc, fs, S1, out_idx1, out_pts1, out_packed1, pts_packed1);
+    G.l1 = fps_args(pts, N, C, sb, sn, sc, start1, S1, out_idx1, out_pts1, out_packed1, pts_packed1);
     G.start2 = start2;
     G.S2 = (int)S2;
     G.out_idx2 = out_idx2;
@@ -458,12 +476,7 @@ extern "C" int pn2_debug_fps_stamps(unsigned long long *out) {
 int pn2::fps_side_check(const pn2_fps_side &f) {
     PN2_REQUIRE(f.start_host, "pn2_fps_side: null start_host");
     const int rc = fps_check(f.pts, f.start_host, f.out_idx, f.B, f.N, f.C, f.S, nullptr, 0);
-    if (rc != PN2_OK) return rc;
-    for (int64_t b = 0; b < f.B; ++b)
-        PN2_REQUIRE(f.start_host[b] >= 0 && f.start_host[b] < f.N,
-                    "pn2_fps_side: start[%lld] = %lld outside [0, %lld)", (long long)b,
-                    (long long)f.start_host[b], (long long)f.N);
-    return PN2_OK;
+    return rc != PN2_OK ? rc : fps_host_starts_check("pn2_fps_side", f.start_host, f.B, f.N);
 }
 
 int pn2::fps_side_launch(const pn2_fps_side &f, hipStream_t st) {
@@ -477,10 +490,8 @@ int pn2::fps_side_launch(const pn2_fps_side &f, hipStream_t st) {
 bool pn2::fps_side_block_args(const pn2_fps_side &f, size_t lds_avail, FpsArgs &F) {
     if (f.B < 1 || f.B > kFpsArgStarts || f.N > 512 || f.S > kFpsMaxS || (f.C != 3 && f.C != 10)) return false;
     if (fps_block_lds(256, (int)f.C, true, f.N, f.S) > lds_avail) return false;
-    FpsStart fs;
-    fs.dev = nullptr;
-    for (int64_t b = 0; b < f.B; ++b) fs.v[b] = (int)f.start_host[b];
-    F = fps_args(f.pts, f.N, f.C, f.sb, f.sn, f.sc, fs, f.S, f.out_idx, f.out_pts, f.out_packed, f.pts_packed);
+    F = fps_args(f.pts, f.N, f.C, f.sb, f.sn, f.sc, nullptr, f.S, f.out_idx, f.out_pts, f.out_packed, f.pts_packed);
+    fps_host_starts(F.start, f.start_host, f.B);
     return true;
 }
 

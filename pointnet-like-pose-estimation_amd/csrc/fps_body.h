@@ -48,9 +48,6 @@ struct FpsArgs {
     FpsStart start;
 };
 
-FpsArgs fps_args(const float *pts, int64_t N, int64_t C, int64_t sb, int64_t sn, int64_t sc,
-                 const FpsStart &start, int64_t S, int64_t *out_idx, float *out_pts, float *out_packed,
-                 float *pts_packed);
 bool fps_side_block_args(const pn2_fps_side &f, size_t lds_avail, FpsArgs &F);
 
 // Per-link cycle breakdown of the serial loop (diagnostic builds only, -DPN2_FPS_STAMPS:

@@ -35,11 +35,9 @@
 // iteration thread t walks the points t, t + kPtsThreads, ..., re-reading x, y, z (L2 hits after
 // the first iteration), and keeps the running distance -- in LDS when the launch's largest cloud
 // fits (DL), else in the caller's workspace, one element per input row -- and its best
-// (distance bits, index) pair: greater bits win, equal bits the smaller index.  The same rule
-// merges the pairs across the wave (shuffles) and across the waves (one LDS slot per wave,
-// double-buffered by iteration parity: ONE barrier per iteration, every thread reduces the
-// slots).  A point's distance element is only ever touched by its own thread.  The indices go
-// straight to out_idx; the gather pass after the loop reads them back.
+// (distance bits, index) pair, which wg_argmax (below) merges across the workgroup by
+// np.argmax's rule.  A point's distance element is only ever touched by its own thread.  The
+// indices go straight to out_idx; the gather pass after the loop reads them back.
 #include "pn2_internal.h"
 
 namespace pn2 {
@@ -47,7 +45,7 @@ namespace pn2 {
 constexpr int kPtsThreads = 1024;
 constexpr int kPtsWaves = kPtsThreads / 64;
 constexpr size_t kPtsLds = (size_t)160 * 1024;
-// [2][waves] 64-bit distance bits, then [2][waves] int indices
+// wg_argmax slots: [2][waves] distance bits (room for 64-bit ones), then [2][waves] int indices
 constexpr size_t kPtsLdsHead = (size_t)2 * kPtsWaves * (8 + 4);
 
 template <typename T> struct PtsBits;
@@ -76,11 +74,32 @@ __device__ __forceinline__ T pts_add(T a, T b) {
     return a + b;
 }
 
-// np.argmax's order on (bits, index) pairs: the greater distance, then the smaller index.  A
-// thread without a point holds (0, INT32_MAX), which loses to every real pair.
+// ---- workgroup argmax, "the first index of the maximum" (np.argmax), on (bits,
+// index) pairs, bits the unsigned pattern of a non-negative distance: greater bits win, on equal
+// bits the smaller index.  A thread without a point holds (0, INT32_MAX), which loses to every
+// real pair.
 template <typename U>
-__device__ __forceinline__ bool pts_better(U ab, int ai, U bb, int bi) {
-    return ab > bb || (ab == bb && ai < bi);
+__device__ __forceinline__ void argmax_take(U &bits, int &idx, U ob, int oi) {
+    static_assert(sizeof(U) == 4 || sizeof(U) == 8, "unsigned or unsigned long long bits");
+    const bool take = (ob > bits) | ((ob == bits) & (oi < idx));  // two selects, no branch
+    bits = take ? ob : bits, idx = take ? oi : idx;
+}
+// Every thread of a workgroup of NW waves brings its pair and leaves with the workgroup's best:
+// wave merge by shuffles, one LDS slot per wave (sbits / sidx: [2][NW]), ONE barrier, every
+// thread merges the NW slots.  The slots are double-buffered by the caller's iteration parity
+// `par`, which is why one barrier suffices: a thread writing parity p in iteration i + 2 has
+// passed the barrier of iteration i + 1, which no thread reaches before it has finished reading
+// iteration i's slots of parity p.
+template <int NW, typename U>
+__device__ __forceinline__ void wg_argmax(U &bits, int &idx, U *sbits, int *sidx, int par) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) argmax_take(bits, idx, __shfl_xor(bits, o), __shfl_xor(idx, o));
+    sbits += par * NW, sidx += par * NW;
+    if ((threadIdx.x & 63) == 0) sbits[threadIdx.x >> 6] = bits, sidx[threadIdx.x >> 6] = idx;
+    __syncthreads();
+    bits = sbits[0], idx = sidx[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) argmax_take(bits, idx, sbits[w], sidx[w]);
 }
 
 template <typename T, bool DL>
@@ -92,7 +111,7 @@ __global__ __launch_bounds__(kPtsThreads) void fps_points_kernel(
     typedef typename PtsBits<T>::type U;
     constexpr int NT = kPtsThreads, NW = kPtsWaves;
     extern __shared__ __attribute__((aligned(16))) unsigned long long psm[];
-    unsigned long long *skey = psm;                           // [2][NW]
+    U *sbits = reinterpret_cast<U *>(psm);                    // [2][NW]
     int *sidx = reinterpret_cast<int *>(psm + 2 * NW);        // [2][NW]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t b = blockIdx.x;
@@ -114,7 +133,7 @@ __global__ __launch_bounds__(kPtsThreads) void fps_points_kernel(
         if (tid == 0) oi[i] = far;
         if (i == S - 1) break;  // the last iteration's update feeds no further argmax
         U best = 0;
-        int bidx = INT32_MAX;
+        far = tid < N ? tid : INT32_MAX;  // the thread's first point holds any tie at 0
         for (int n = tid; n < N; n += NT) {
             const T *q = P + (int64_t)n * ld;
             const T d0 = pts_sub(q[0], c0), d1 = pts_sub(q[1], c1), d2 = pts_sub(q[2], c2);
@@ -125,26 +144,9 @@ __global__ __launch_bounds__(kPtsThreads) void fps_points_kernel(
                 dist[n] = dd;
             }
             const U bits = PtsBits<T>::of(cur);
-            if (pts_better<U>(bits, n, best, bidx)) best = bits, bidx = n;
+            if (bits > best) best = bits, far = n;  // n ascends: the first index of the thread's maximum
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const U ob = __shfl_xor(best, o);
-            const int oj = __shfl_xor(bidx, o);
-            if (pts_better<U>(ob, oj, best, bidx)) best = ob, bidx = oj;
-        }
-        const int par = i & 1;
-        if (lane == 0) skey[par * NW + wave] = best, sidx[par * NW + wave] = bidx;
-        __syncthreads();  // the other parity's slots were last read before this barrier
-        U g = (U)skey[par * NW];
-        int gi = sidx[par * NW];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) {
-            const U ob = (U)skey[par * NW + w];
-            const int oj = sidx[par * NW + w];
-            if (pts_better<U>(ob, oj, g, gi)) g = ob, gi = oj;
-        }
-        far = gi;
+        wg_argmax<NW>(best, far, sbits, sidx, i & 1);
         c0 = P[(int64_t)far * ld], c1 = P[(int64_t)far * ld + 1], c2 = P[(int64_t)far * ld + 2];
     }
     __syncthreads();

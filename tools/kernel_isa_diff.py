@@ -6,6 +6,9 @@ Each tree's pointnet-like-pose-estimation_amd/csrc/<source> is compiled to gfx95
 the flags csrc/Makefile of that tree gives the file (make -n; --offload-device-only -S as its
 ASMCHECK rule).  Per kernel symbol: "same" when the instructions are equal line by line (comments
 and directives stripped, labels kept), else both instruction counts and the first differing line.
+The kernel descriptor's resource numbers (next free VGPR / SGPR, accumulator offset, LDS and
+scratch bytes) are compared with the instructions and printed wherever anything differs.
+A kernel whose parameter list changed is paired by its name and template arguments.
 Host only; it compares and searches for nothing.  Exit status 1 when any kernel differs."""
 import json
 import os
@@ -53,24 +56,47 @@ def kernels(text):
     return out
 
 
+RESOURCES = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "group_segment_fixed_size",
+             "private_segment_fixed_size")
+
+
+def resources(text):
+    """{symbol: {descriptor field: value}} from the .amdhsa_kernel blocks."""
+    out = {}
+    for sym, body in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)\n(.*?)\.end_amdhsa_kernel", text, re.M | re.S):
+        out[sym] = {k: int(v, 0) for k, v in re.findall(r"\.amdhsa_(\w+)\s+(\w+)", body) if k in RESOURCES}
+    return out
+
+
 def main():
     a, b, source = sys.argv[1:4]
     with ThreadPoolExecutor(2) as ex:  # the two compilations side by side
-        ka, kb = (kernels(t) for t in ex.map(lambda tree: assembly(tree, source), (a, b)))
-    names = subprocess.run(["c++filt"], input="\n".join(sorted(ka)), capture_output=True, text=True).stdout.split("\n")
-    report, diff = {}, 0
+        ta, tb = ex.map(lambda tree: assembly(tree, source), (a, b))
+    ka, kb, ra, rb = kernels(ta), kernels(tb), resources(ta), resources(tb)
+
+    def demangled(syms):
+        return subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")
+
+    names = demangled(sorted(ka))
+    by_name = {n.split("(")[0]: s for s, n in zip(sorted(kb), demangled(sorted(kb)))}
+    report, diff, paired = {}, 0, set()
     for sym, name in zip(sorted(ka), names):
+        if sym not in kb and name.split("(")[0] in by_name:  # same kernel, other parameters
+            sb = by_name[name.split("(")[0]]
+            kb[sym], rb[sym] = kb[sb], rb[sb]
+            paired.add(sb)
         x, y = ka[sym], kb.get(sym)
         if y is None:
             report[name] = "missing in B"
-        elif x == y:
+        elif x == y and ra[sym] == rb[sym]:
             report[name] = "same (%d)" % len(x)
         else:
             i = next((i for i, (p, q) in enumerate(zip(x, y)) if p != q), min(len(x), len(y)))
-            report[name] = "DIFF %d vs %d, first at %d: %r | %r" % (len(x), len(y), i, "".join(x[i:i + 1]), "".join(y[i:i + 1]))
+            report[name] = "DIFF %d vs %d, first at %d: %r | %r; resources %s | %s" % (
+                len(x), len(y), i, "".join(x[i:i + 1]), "".join(y[i:i + 1]), ra[sym], rb[sym])
         diff += report[name][:4] != "same"
-        print("%-100s %s" % (name[:100], report[name]))
-    for sym in sorted(set(kb) - set(ka)):
+        print("%-100s %s" % (name[:100] if report[name][:4] == "same" else name, report[name]))
+    for sym in sorted(set(kb) - set(ka) - paired):
         diff += 1
         report[sym] = "only in B"
         print("%s only in B" % sym)
