@@ -57,7 +57,7 @@ from . import geometry
 from . import ops
 from . import shard
 from . import tuning
-from .pointnet2_utils import PointNetSetAbstraction, PointNetSetAbstractionMsg, msg_ball_queries
+from .pointnet2_utils import PointNetSetAbstraction, PointNetSetAbstractionMsg, _ball_queries
 
 
 def _cu_count(device):
@@ -311,7 +311,7 @@ class PipelinedForward:
             second = None  # the chain's second layer, sampled in its first layer's launch
             # single-scale layers only: the MSG heads keep their two launches
             if i not in first and len(ch) > 1 and \
-                    not any(isinstance(sa, PointNetSetAbstractionMsg) for sa in ch[:2]) and \
+                    all(len(sa._scales()) == 1 for sa in ch[:2]) and \
                     ops.fps2_eligible(N, p.shape[2], ch[0].point_number, ch[1].point_number):
                 r1, r2 = ops.fps2_direct(p, ch[0].point_number, ch[1].point_number,
                                          starts[id(ch[0])], starts[id(ch[1])])
@@ -325,12 +325,7 @@ class PipelinedForward:
                     newp, cpk, ppk = second
                 else:
                     _, newp, cpk, ppk = ops.fps_direct(p, sa.point_number, starts[id(sa)])
-                if not bq:
-                    idxs = []
-                elif isinstance(sa, PointNetSetAbstractionMsg):
-                    idxs = msg_ball_queries(ppk, cpk, C, sa.radius_list, sa.sample_number_list)
-                else:
-                    idxs = [ops.ball_query_direct(ppk, cpk, C, sa.radius, sa.sample_number, True)]
+                idxs = _ball_queries(sa, ppk, cpk, C) if bq else []
                 entries[id(sa)] = (p.data_ptr(), newp, cpk, ppk, idxs)
                 p = newp
         return entries

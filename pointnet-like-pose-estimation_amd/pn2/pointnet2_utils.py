@@ -11,9 +11,14 @@ MLP):
   pn2::fps            FPS + gathered centroids + packed (coords, ssq) records
   pn2::ball_query     first-K-in-radius neighbour indices
   pn2::sa_mlp_max_    fused gather -> conv1x1/BN/ReLU chain -> max over neighbours
-(+ per scale for the MSG module).  Hidden activations stay in registers (the chain kernel) or
-pass through an HBM workspace between the dense-layer launches (group_all layers); the
-per-layer ``[B, C, K, S]`` tensors of the reference are never materialised.
+(the last one per scale; an MSG layer's ball queries are one launch over its radii).  Hidden
+activations stay in registers (the chain kernel) or pass through an HBM workspace between the
+dense-layer launches (group_all layers); the per-layer ``[B, C, K, S]`` tensors of the
+reference are never materialised.
+
+The two modules are the reference's constructors over one layer body (_SetAbstraction) written
+over the module's list of scales; whatever else needs a layer's scales (_ball_queries,
+_eval_grad_route, pn2.pipeline) reads ``_scales()`` too, never the class.
 
 Training (``model.train()`` or autograd through the weights) keeps the reference's semantics
 (batch-statistics BatchNorm, autograd through the MLP and the feature gather): FPS and the ball
@@ -82,9 +87,21 @@ def msg_ball_queries(ppk, cpk, C, radii, nsamples):
     """The ball queries of an MSG layer's scales (pointnet2_utils.py:197-203): one launch over
     all radii (ops.ball_query_multi_direct; host tuning bq_multi = 0: one call per radius), the
     same (int32 lists, counts) per radius either way."""
-    if tuning.get("bq_multi") and len(radii) > 1:
+    if len(radii) > 1 and tuning.get("bq_multi"):
         return ops.ball_query_multi_direct(ppk, cpk, C, radii, nsamples)
     return [ops.ball_query_direct(ppk, cpk, C, r, k, True) for r, k in zip(radii, nsamples)]
+
+
+def _ball_queries(module, ppk, cpk, C):
+    """The ball queries of an SA module's scales on packed points / centroids (the module body
+    and pn2.pipeline's geometry pre-computation) -> [(int32 lists, counts)] per scale."""
+    scales = module._scales()
+    return msg_ball_queries(ppk, cpk, C, [s[0] for s in scales], [s[1] for s in scales])
+
+
+def _cat_scales(outs):
+    """The scales' [B, Cout, S] outputs as one (:221); a single scale's is returned as it is."""
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
 
 def _channels_last(feature):
@@ -161,10 +178,7 @@ def _eval_grad_route(module, points, feature):
         return False  # non-float32 tensors (or host tensors): torch formulation
     if _precision(module) != "fp32":  # bf16 forward: the float32 recompute is another function
         return False
-    if isinstance(module, PointNetSetAbstractionMsg):
-        blocks = list(zip(module.conv_blocks, module.bn_blocks))
-    else:
-        blocks = [(module.mlp_convs, module.mlp_bns)]
+    blocks = [(convs, bns) for _, _, convs, bns, _ in module._scales()]
     for convs, _ in blocks:  # shapes the fused MLP entry rejects (widths not x32, > 4 layers)
         if not ops.sa_mlp_supported(c.weight.shape[0] for c in convs):
             return False
@@ -356,8 +370,122 @@ def sample_and_group_all(points, feature):
 
 
 # ----------------------------------------------------------------------------- modules
-class PointNetSetAbstraction(nn.Module):
+class _SetAbstraction(nn.Module):
+    """The layer body of both SA modules, written over the module's scales.  A module gives
+    ``_scales()`` -> [(radius, nsample, convs, bns, pack cache)] (one entry for SSG, one per
+    radius for MSG; read from the live attributes on every call) and its grouped-row order:
+    ``_xyz_first`` (the reference's rows are [xyz | feature] in SSG, :114 / :139, and
+    [feature | xyz] in MSG, :209) with the fused kernels' source mode ``_src`` for it."""
+
+    group_all = False
+
+    def forward(self, points, feature):
+        """points [B,C,N], feature [B,D,N] or None -> (new_points [B,C,S], new_feature
+        [B, sum of mlp[-1] over the scales, S]).  Both outputs are channel-first views of
+        channels-last buffers."""
+        if _needs_autograd(self, points, feature):
+            if _eval_grad_route(self, points, feature):
+                return _eval_grad_forward(self, points, feature)
+            return self._forward_autograd(points, feature)
+        new_points, out, _, _ = self._fused_body(points, feature)
+        return self._views(new_points, out)
+
+    def _views(self, new_points, out):
+        """The fused body's buffers as the forward's channel-first outputs."""
+        B, cout = new_points.shape[0], out.shape[-1]
+        if self.group_all:
+            return new_points, out.view(B, 1, cout).permute(0, 2, 1)
+        return new_points.permute(0, 2, 1), out.view(B, -1, cout).permute(0, 2, 1)
+
+    def _fused_body(self, points, feature, live=False):
+        """The fused inference launches of all scales (the no_grad forward and _SaEvalGrad's
+        forward) -> (new_points buffer, out rows, centroids [B,S,C] or None, [int32 neighbour
+        lists per scale])."""
+        pts = points.permute(0, 2, 1)
+        feat = None if feature is None else _channels_last(feature)
+        B, N, C = pts.shape
+        dev = pts.device
+        scales = self._scales()
+        # the fp32 kernels read [feature | xyz]: leading xyz channels rotate behind the features;
+        # the split-bf16 rows keep the module's order (group_all layers too)
+        rot0 = C if self._xyz_first and feat is not None else 0
+        chains = [_pack_chain(convs, bns, cache, rot0, C, self._xyz_first)
+                  for _, _, convs, bns, cache in scales]
+        total = sum(ch[0][-1].shape[1] for ch in chains)
+        if self.group_all:
+            wts, als, bes, cins, splits = chains[0]
+            out = torch.empty(B, total, device=dev, dtype=torch.float32)
+            # new_points = the reference's zeros (:136), filled by the MLP's last launch
+            new_points = torch.empty(B, C, 1, device=dev, dtype=torch.float32)
+            ops.sa_mlp_max_direct(out, _lib.SRC_GROUP_ALL, pts, feat, None, None, wts, als, bes, cins,
+                                  splits, _precision(self), zero=new_points)
+            return new_points, out, None, []
+        S = self.point_number
+        pre = geometry.take(self, pts)  # FPS (+ ball queries) precomputed by pn2.pipeline
+        if pre is not None:
+            new_points, cpk, ppk, idxs = pre
+            if not idxs:
+                idxs = _ball_queries(self, ppk, cpk, C)
+        else:
+            with geometry.Span(dev, [pts]) as span:  # overlaps the previous layer's MLP
+                _, new_points, cpk, ppk = ops.fps_direct(pts, S, _draw_start(B, N, dev))
+                idxs = _ball_queries(self, ppk, cpk, C)
+            span.finish([new_points], [new_points] + [t for ic in idxs for t in ic])
+        out = torch.empty(B * S, total, device=dev, dtype=torch.float32)
+        prec = _precision(self)
+        col = 0
+        side = _fps_ahead(self, new_points, live)  # rides on the longest scale's launch (largest K)
+        longest = max(range(len(scales)), key=lambda i: scales[i][1])
+        for i, (idx, cnt) in enumerate(idxs):
+            wts, als, bes, cins, splits = chains[i]
+            cout = wts[-1].shape[1]
+            ops.sa_mlp_max_impl(out[:, col:col + cout], self._src, pts, feat, new_points, idx, wts,
+                                als, bes, cins, splits, prec, cnt=cnt,
+                                fps_side=side if i == longest else None)
+            col += cout
+        return new_points, out, new_points, [idx for idx, _ in idxs]
+
+    def _recompute(self, points, feature, centers, idxs):
+        """Every scale again from the forward's centroids and lists, differentiable in `feature`
+        and the parameters, on the frozen-statistics training kernels (one Function for the
+        module: autograd sums the scales' feature gradients) -> [B, sum Cout, S]."""
+        pts = points.permute(0, 2, 1)
+        feat = None if feature is None else feature.permute(0, 2, 1)
+        scales = self._scales()
+        if self.group_all:  # plain rows in the reference's [xyz | feature] order (:139)
+            _, _, convs, bns, _ = scales[0]
+            return train.mlp_max_frozen(sample_and_group_all(pts, feat)[1], convs, bns)
+        outs = []
+        for idx, (_, _, convs, bns, _) in zip(idxs, scales):
+            grouped = _frozen_group(pts, idx, centers, feat, not self._xyz_first)
+            outs.append(train.mlp_max_frozen(grouped, convs, bns))
+        return _cat_scales(outs)
+
+    def _forward_autograd(self, points, feature):
+        """The torch formulation (training, and what _eval_grad_route leaves to it): FPS and the
+        ball queries as HIP kernels, grouping and MLP + max under autograd."""
+        pts = points.permute(0, 2, 1)
+        feat = None if feature is None else feature.permute(0, 2, 1)
+        scales = self._scales()
+        if self.group_all:
+            _, _, convs, bns, _ = scales[0]
+            new_points, grouped = sample_and_group_all(pts, feat)
+            return new_points.permute(0, 2, 1), _torch_mlp_max(grouped, convs, bns)
+        B, N, C = pts.shape
+        _, new_points, cpk, ppk = ops.fps_direct(pts.detach(), self.point_number,
+                                                 _draw_start(B, N, pts.device))
+        outs = []
+        for radius, nsample, convs, bns, _ in scales:
+            idx = ops.ball_query_direct(ppk, cpk, C, radius, nsample)
+            grouped = _torch_group(pts, idx, new_points, feat, not self._xyz_first)
+            outs.append(_torch_mlp_max(grouped, convs, bns))
+        return new_points.permute(0, 2, 1), _cat_scales(outs)
+
+
+class PointNetSetAbstraction(_SetAbstraction):
     """pointnet2_utils.py:143-174 (same ctor, submodule names and forward contract)."""
+
+    _xyz_first, _src = True, _lib.SRC_GROUP_XYZ_FIRST
 
     def __init__(self, point_number, sample_number, radius, in_channel, mlp, group_all=False):
         super(PointNetSetAbstraction, self).__init__()
@@ -375,86 +503,14 @@ class PointNetSetAbstraction(nn.Module):
         self._pack_cache = {}
         self.mlp_precision = None  # None: ops.mlp_precision context ("fp32" by default)
 
-    def forward(self, points, feature):
-        """points [B,C,N], feature [B,D,N] or None -> (new_points [B,C,S], new_feature
-        [B,mlp[-1],S]).  Both outputs are channel-first views of channels-last buffers."""
-        if _needs_autograd(self, points, feature):
-            if _eval_grad_route(self, points, feature):
-                return _eval_grad_forward(self, points, feature)
-            return self._forward_autograd(points, feature)
-        new_points, out, _, _ = self._fused_body(points, feature)
-        return self._views(new_points, out)
-
-    def _views(self, new_points, out):
-        """The fused body's buffers as the forward's channel-first outputs."""
-        B, cout = new_points.shape[0], out.shape[-1]
-        if self.group_all:
-            return new_points, out.view(B, 1, cout).permute(0, 2, 1)
-        return new_points.permute(0, 2, 1), out.view(B, -1, cout).permute(0, 2, 1)
-
-    def _fused_body(self, points, feature, live=False):
-        """The fused inference launches (the no_grad forward and _SaEvalGrad's forward) ->
-        (new_points buffer, out rows, centroids [B,S,C] or None, [int32 neighbour lists])."""
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else _channels_last(feature)
-        B, N, C = pts.shape
-        # reference row order is [xyz, feature] (:114, :139); kernels use [feature, xyz]
-        rot0 = C if feat is not None else 0
-        xyz = C  # split-bf16 rows are [xyz | features] for grouped and group_all layers alike
-        wts, als, bes, cins, splits = _pack_chain(self.mlp_convs, self.mlp_bns, self._pack_cache,
-                                                  rot0, xyz, True)
-        cout = wts[-1].shape[1]
-        dev = pts.device
-        if self.group_all:
-            out = torch.empty(B, cout, device=dev, dtype=torch.float32)
-            # new_points = the reference's zeros (:136), filled by the MLP's last launch
-            new_points = torch.empty(B, C, 1, device=dev, dtype=torch.float32)
-            ops.sa_mlp_max_direct(out, _lib.SRC_GROUP_ALL, pts, feat, None, None, wts, als, bes, cins,
-                                  splits, _precision(self), zero=new_points)
-            return new_points, out, None, []
-        S, K = self.point_number, self.sample_number
-        pre = geometry.take(self, pts)  # FPS (+ ball query) precomputed by pn2.pipeline
-        if pre is not None:
-            new_points, cpk, ppk, idxs = pre
-            idx, cnt = idxs[0] if idxs else ops.ball_query_direct(ppk, cpk, C, self.radius, K, True)
-        else:
-            with geometry.Span(dev, [pts]) as span:  # overlaps the previous layer's MLP
-                _, new_points, cpk, ppk = ops.fps_direct(pts, S, _draw_start(B, N, dev))
-                idx, cnt = ops.ball_query_direct(ppk, cpk, C, self.radius, K, True)
-            span.finish([new_points], [new_points, idx, cnt])
-        out = torch.empty(B * S, cout, device=dev, dtype=torch.float32)
-        ops.sa_mlp_max_impl(out, _lib.SRC_GROUP_XYZ_FIRST, pts, feat, new_points, idx, wts, als, bes,
-                            cins, splits, _precision(self), cnt=cnt,
-                            fps_side=_fps_ahead(self, new_points, live))
-        return new_points, out, new_points, [idx]
-
-    def _recompute(self, points, feature, centers, idxs):
-        """The layer again from the forward's centroids and lists, differentiable in `feature`
-        and the parameters, on the frozen-statistics training kernels -> [B, Cout, S]."""
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else feature.permute(0, 2, 1)
-        if self.group_all:  # plain rows in the reference's [xyz | feature] order (:139)
-            grouped = sample_and_group_all(pts, feat)[1]
-        else:
-            grouped = _frozen_group(pts, idxs[0], centers, feat, False)
-        return train.mlp_max_frozen(grouped, self.mlp_convs, self.mlp_bns)
-
-    def _forward_autograd(self, points, feature):
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else feature.permute(0, 2, 1)
-        if self.group_all:
-            new_points, grouped = sample_and_group_all(pts, feat)
-        else:
-            B, N, C = pts.shape
-            _, new_points, cpk, ppk = ops.fps_direct(pts.detach(), self.point_number,
-                                              _draw_start(B, N, pts.device))
-            idx = ops.ball_query_direct(ppk, cpk, C, self.radius, self.sample_number)
-            grouped = _torch_group(pts, idx, new_points, feat, False)
-        return new_points.permute(0, 2, 1), _torch_mlp_max(grouped, self.mlp_convs, self.mlp_bns)
+    def _scales(self):
+        return [(self.radius, self.sample_number, self.mlp_convs, self.mlp_bns, self._pack_cache)]
 
 
-class PointNetSetAbstractionMsg(nn.Module):
+class PointNetSetAbstractionMsg(_SetAbstraction):
     """pointnet2_utils.py:176-223 (same ctor, submodule names and forward contract)."""
+
+    _xyz_first, _src = False, _lib.SRC_GROUP_FEAT_FIRST
 
     def __init__(self, point_number, sample_number_list, radius_list, in_channel, mlp_list,
                  num_category=0):
@@ -477,78 +533,9 @@ class PointNetSetAbstractionMsg(nn.Module):
         self._pack_cache = [{} for _ in mlp_list]
         self.mlp_precision = None  # None: ops.mlp_precision context ("fp32" by default)
 
-    def forward(self, points, feature):
-        if _needs_autograd(self, points, feature):
-            if _eval_grad_route(self, points, feature):
-                return _eval_grad_forward(self, points, feature)
-            return self._forward_autograd(points, feature)
-        new_points, out, _, _ = self._fused_body(points, feature)
-        return self._views(new_points, out)
-
-    def _views(self, new_points, out):
-        B, total = new_points.shape[0], out.shape[-1]
-        return new_points.permute(0, 2, 1), out.view(B, -1, total).permute(0, 2, 1)
-
-    def _fused_body(self, points, feature, live=False):
-        """The fused inference launches of all scales (the no_grad forward and _SaEvalGrad's
-        forward) -> (new_points [B,S,C], out rows, centroids, [int32 lists per scale])."""
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else _channels_last(feature)
-        B, N, C = pts.shape
-        S = self.point_number
-        dev = pts.device
-        # MSG row order is already [feature, xyz] (:209): no rotation
-        chains = [_pack_chain(self.conv_blocks[i], self.bn_blocks[i], self._pack_cache[i], 0, C,
-                              False)
-                  for i in range(len(self.radius_list))]
-        total = sum(ch[0][-1].shape[1] for ch in chains)
-        pre = geometry.take(self, pts)  # FPS (+ ball queries) precomputed by pn2.pipeline
-        if pre is not None:
-            new_points, cpk, ppk, idxs = pre
-            if not idxs:
-                idxs = msg_ball_queries(ppk, cpk, C, self.radius_list, self.sample_number_list)
-        else:
-            with geometry.Span(dev, [pts]) as span:  # overlaps the previous layer's MLP
-                _, new_points, cpk, ppk = ops.fps_direct(pts, S, _draw_start(B, N, dev))
-                idxs = msg_ball_queries(ppk, cpk, C, self.radius_list, self.sample_number_list)
-            span.finish([new_points], [new_points] + [t for ic in idxs for t in ic])
-        out = torch.empty(B * S, total, device=dev, dtype=torch.float32)
-        prec = _precision(self)
-        col = 0
-        side = _fps_ahead(self, new_points, live)  # rides on the longest scale's launch (largest K)
-        longest = max(range(len(idxs)), key=lambda i: self.sample_number_list[i])
-        for i, (idx, cnt) in enumerate(idxs):
-            wts, als, bes, cins, splits = chains[i]
-            cout = wts[-1].shape[1]
-            ops.sa_mlp_max_impl(out[:, col:col + cout], _lib.SRC_GROUP_FEAT_FIRST, pts, feat,
-                                new_points, idx, wts, als, bes, cins, splits, prec, cnt=cnt,
-                                fps_side=side if i == longest else None)
-            col += cout
-        return new_points, out, new_points, [idx for idx, _ in idxs]
-
-    def _recompute(self, points, feature, centers, idxs):
-        """Every scale again from the forward's centroids and lists (one Function for the module:
-        autograd sums the scales' feature gradients) -> [B, sum Cout, S]."""
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else feature.permute(0, 2, 1)
-        outs = []
-        for i, idx in enumerate(idxs):
-            grouped = _frozen_group(pts, idx, centers, feat, True)
-            outs.append(train.mlp_max_frozen(grouped, self.conv_blocks[i], self.bn_blocks[i]))
-        return torch.cat(outs, dim=1)
-
-    def _forward_autograd(self, points, feature):
-        pts = points.permute(0, 2, 1)
-        feat = None if feature is None else feature.permute(0, 2, 1)
-        B, N, C = pts.shape
-        _, new_points, cpk, ppk = ops.fps_direct(pts.detach(), self.point_number,
-                                          _draw_start(B, N, pts.device))
-        outs = []
-        for i, radius in enumerate(self.radius_list):
-            idx = ops.ball_query_direct(ppk, cpk, C, radius, self.sample_number_list[i])
-            grouped = _torch_group(pts, idx, new_points, feat, True)
-            outs.append(_torch_mlp_max(grouped, self.conv_blocks[i], self.bn_blocks[i]))
-        return new_points.permute(0, 2, 1), torch.cat(outs, dim=1)
+    def _scales(self):
+        return list(zip(self.radius_list, self.sample_number_list, self.conv_blocks, self.bn_blocks,
+                        self._pack_cache))
 
 
 __all__ = [
