@@ -82,6 +82,9 @@
  *                          the capture scripts' clip_distance, delet_outlier_radius, cluster_point
  *                                                            point_collect/collect.py:30-102;
  *                                                            camera_test/camera.py:131
+ *   pn2_knn_mean_dist_f64 / pn2_stat_outlier_flags
+ *                          the capture scripts' delet_outlier_statistical
+ *                                                            point_collect/collect.py:80-90
  */
 #ifndef PN2_H
 #define PN2_H
@@ -295,6 +298,48 @@ int64_t pn2_dbscan_labels_workspace_bytes(int64_t N);
 int pn2_dbscan_labels(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld, double eps,
                       int64_t min_points, const int32_t *counts, int32_t *labels, int64_t *nclusters,
                       void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- statistical outlier removal: delet_outlier_statistical (point_collect/collect.py:80-90;
+ * csrc/knn.hip), Open3D's RemoveStatisticalOutliers with its kd-tree replaced by exact arithmetic.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * The cloud is the camera-cloud front end's (above): pts [N][ld], 3 <= C <= 64, float32 or float64,
+ * N <= pn2_collect_max_points().  k = nb_neighbors, 1 <= k <= pn2_knn_max_k() = 256.
+ *  S1 Candidates.  A row is finite when its three coordinates are finite.  Only finite rows are
+ *     candidates and queries.  F = the number of finite rows, k_eff = min(k, F).
+ *  S2 Distance.  d2(i,j) is rule 2's: ((dx*dx) + (dy*dy)) + (dz*dz) in float64 (float32 inputs
+ *     widened first), every operation rounded once, no contraction.
+ *  S3 Mean distance.  For a finite row i: the k_eff smallest d2(i,j) over all finite j (i itself
+ *     included, d2 = 0), sorted ascending; the correctly rounded sqrt of each; added in that order as
+ *     one float64 chain from 0.0; divided once by (double)k_eff.  Ties at the k-th place carry equal
+ *     values, so the bits do not depend on which tied row is taken.  mean[i] = -1.0 for a non-finite
+ *     row.
+ *  S4 Cloud statistics.  valid = F.  cloud_mean = (sum of mean[i], i ascending, only the terms with
+ *     mean[i] > 0) / valid.  sq_sum = sum over i ascending of (mean[i] - cloud_mean) * (mean[i] -
+ *     cloud_mean) where mean[i] > 0, else of 0.  std = sqrt(sq_sum / (valid - 1)).  threshold =
+ *     cloud_mean + std_ratio * std.  Each sum is one float64 chain in index order; every operation
+ *     is rounded once.  valid == 1 gives 0/0 = NaN and nothing is kept: IEEE, no special case.
+ *  S5 Selection.  Row i is kept iff mean[i] > 0 && mean[i] < threshold, in input order.  A row whose
+ *     k_eff nearest rows are all its duplicates has mean 0 and is dropped, as Open3D drops it.
+ *     F == 0 or N == 0: nothing is kept.
+ *
+ * pn2_knn_mean_dist_f64   mean [N] float64 (device) by S1-S3.  Brute force over N * N pairs: the
+ *                         candidates staged in LDS tiles, a wave per few queries, a ballot against
+ *                         the query's current k-th value, the survivors bitonic-sorted in LDS.  No
+ *                         atomics: two runs give the same bits.  k < 1: PN2_EINVAL; k >
+ *                         pn2_knn_max_k(): PN2_EUNSUPPORTED.  Workspace (the float64 coordinates):
+ *                         pn2_knn_mean_dist_workspace_bytes(N, k) bytes, 16-byte aligned (-1: bad
+ *                         arguments).
+ * pn2_stat_outlier_flags  one launch of one workgroup, no host read: stats [4] float64 (device) =
+ *                         {cloud_mean, std, threshold, (double)valid} by S4 and flags[i] = 1 / 0
+ *                         (int32 [N]) by S5 from mean [N].  std_ratio <= 0: PN2_EINVAL.  The kept
+ *                         rows are pn2_compact_rows(flags, PN2_COMPACT_FLAG_GT, thresh = 0).
+ * N == 0: PN2_OK, nothing is written, no launch. */
+int64_t pn2_knn_max_k(void);
+int64_t pn2_knn_mean_dist_workspace_bytes(int64_t N, int64_t k);
+int pn2_knn_mean_dist_f64(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld, int64_t k,
+                          double *mean, void *workspace, int64_t workspace_bytes, void *stream);
+int pn2_stat_outlier_flags(const double *mean, int64_t N, double std_ratio, int32_t *flags,
+                           double *stats, void *stream);
 
 /* Pack a [B,N,C] strided view into [B,N,cp] with its ssq (see above).  C <= 64, as for the
  * ball query and square_distance below (else PN2_EUNSUPPORTED). */

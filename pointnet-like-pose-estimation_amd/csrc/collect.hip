@@ -18,11 +18,10 @@
 //     the stable counting sort of rows by cluster label, whose scan also is the `offsets` table
 //     pn2_fps_points takes.
 //   * small maps (flags, union-find init / flatten / label).
-#include "pn2_internal.h"
+#include "collect_common.h"
 
 namespace pn2 {
 
-constexpr int64_t kCollectMaxN = (int64_t)1 << 20;
 constexpr int kPairThreads = 256;
 // Queries per thread.  float64 adds and multiplies issue at a quarter of the float32 rate, so the
 // three LDS broadcasts per candidate are already hidden behind 2 x 10 VALU operations; a larger
@@ -35,22 +34,11 @@ constexpr int kChunkSteps = kChunk / 64;
 constexpr int64_t kCompactMaxEntries = (int64_t)1 << 26;  // chunks x buckets of one compaction
 
 // ------------------------------------------------------------------------ the neighbour rule
-// d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in float64, every operation rounded once.
-__device__ __forceinline__ double nbr_d2(double ax, double ay, double az, double bx, double by, double bz) {
-#pragma clang fp contract(off)
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
+// (nbr_d2: collect_common.h)
 // j is a neighbour of i iff d2 < r*r.  The strict `<` is a reading of nanoflann's radius result
 // set behind Open3D's SearchRadius that nobody has checked against Open3D: a
 // correction is this one line.
 __device__ __forceinline__ bool nbr_within(double d2, double r2) { return d2 < r2; }
-
-template <typename T>
-__device__ __forceinline__ void load_xyz(const T *pts, int64_t ld, int64_t row, double &x, double &y, double &z) {
-    const T *p = pts + row * ld;
-    x = (double)p[0], y = (double)p[1], z = (double)p[2];
-}
 
 __device__ __forceinline__ int n_of(const int64_t *n_dev, int n_host) {
     if (!n_dev) return n_host;
@@ -328,8 +316,6 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(
     }
 }
 
-static int64_t elem_size(int dtype) { return dtype == PN2_DTYPE_F64 ? 8 : dtype == PN2_DTYPE_F32 ? 4 : 0; }
-static int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 static int64_t chunks_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
 
 struct CompactJob {
@@ -383,18 +369,6 @@ static void pair_launch(const void *pts, int64_t ld, const int *qsel, const int6
     hipLaunchKernelGGL((collect_pair_kernel<T, MODE>), dim3((unsigned)((nq_host + kPairSlab - 1) / kPairSlab)),
                        dim3(kPairThreads), 0, st, static_cast<const T *>(pts), ld, qsel, nq_dev, (int)nq_host, csel,
                        nc_dev, (int)nc_host, r2, out, parent, clabel);
-}
-
-// the checks every entry shares: 0 to go on, else the code to return
-static int check_cloud(const char *who, const void *pts, int dtype, int64_t N, int64_t C, int64_t ld) {
-    PN2_REQUIRE(pts, "%s: null pointer", who);
-    PN2_REQUIRE(elem_size(dtype) != 0, "%s: unknown dtype %d", who, dtype);
-    PN2_REQUIRE(N >= 0 && C >= 3 && C <= kMaxCWide && ld >= C, "%s: bad shape (N=%lld C=%lld ld=%lld; 3 <= C <= 64)",
-                who, (long long)N, (long long)C, (long long)ld);
-    if (N > kCollectMaxN)
-        return set_error(PN2_EUNSUPPORTED, "%s: N=%lld above pn2_collect_max_points() = %lld", who, (long long)N,
-                         (long long)kCollectMaxN);
-    return PN2_OK;
 }
 
 // the int32 arrays of pn2_dbscan_labels' workspace, each padded to 16 bytes

@@ -106,6 +106,10 @@ SIGNATURES = {
                                 _vp]),
     "pn2_dbscan_labels_workspace_bytes": (_i64, [_i64]),
     "pn2_dbscan_labels": (_int, [_vp, _int, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "pn2_knn_max_k": (_i64, []),
+    "pn2_knn_mean_dist_workspace_bytes": (_i64, [_i64, _i64]),
+    "pn2_knn_mean_dist_f64": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "pn2_stat_outlier_flags": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp]),
     "pn2_pack_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pn2_ball_query_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
     "pn2_ball_query_cnt_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp]),

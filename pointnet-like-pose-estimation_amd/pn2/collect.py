@@ -2,9 +2,10 @@
 (point_collect/collect.py:30-102, its copy colledt_data_structure/collect.py, and
 camera_test/camera.py:131): a frame's cloud is cut to a depth range (clip_distance), cleaned of
 sparse points (delet_outlier_radius) and split into objects that are FPS-sampled to a common size
-(cluster_point).  The reference runs them as numpy masks and Open3D kd-tree calls on the host; here
-they are the kernels of csrc/collect.hip plus the existing numpy-rule FPS (csrc/fps_points.hip),
-by the rules include/pn2.h states.  Names, misspellings included, defaults and return shapes are
+(cluster_point); delet_outlier_statistical (collect.py:80-90) is the file's other outlier filter.
+The reference runs them as numpy masks and Open3D kd-tree calls on the host; here they are the
+kernels of csrc/collect.hip and csrc/knn.hip plus the existing numpy-rule FPS
+(csrc/fps_points.hip), by the rules include/pn2.h states.  Names, misspellings included, defaults and return shapes are
 the reference's; cluster_point's `visualize` flag is not carried.
 
 Input is [N, C], 3 <= C <= 64, float64 or float32: a numpy array (the result is a numpy array) or a
@@ -167,4 +168,68 @@ def cluster_point(point_cloud, eps=0.03, min_points=500, device=None):
     return _result(out.double(), host)
 
 
+def _neighbours(who, nb_neighbors):
+    k = int(nb_neighbors)
+    if k < 1:
+        raise ValueError("pn2.collect.%s: nb_neighbors must be >= 1, got %d" % (who, k))
+    limit = _lib.load().pn2_knn_max_k()
+    if k > limit:
+        raise ValueError("pn2.collect.%s: nb_neighbors = %d, above the %d the kernel takes" % (who, k, limit))
+    return k
+
+
+def _knn_mean(t, k):
+    """pn2_knn_mean_dist_f64 -> float64 [N] (include/pn2.h S1-S3); no host read"""
+    N, C = t.shape
+    lib = _lib.load()
+    with torch.cuda.device(t.device):
+        mean = torch.empty(N, dtype=torch.float64, device=t.device)
+        need = lib.pn2_knn_mean_dist_workspace_bytes(N, k)
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
+        _lib.check(lib.pn2_knn_mean_dist_f64(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), k,
+                                             mean.data_ptr(), ws.data_ptr(), need, _stream(mean)),
+                   "pn2_knn_mean_dist_f64")
+    return mean
+
+
+def _stat_flags(mean, std_ratio):
+    """pn2_stat_outlier_flags -> (flags int32 [N], stats float64 [4] = cloud_mean, std, threshold,
+    valid), both on the device; no host read"""
+    N = mean.shape[0]
+    with torch.cuda.device(mean.device):
+        flags = torch.empty(N, dtype=torch.int32, device=mean.device)
+        stats = torch.empty(4, dtype=torch.float64, device=mean.device)
+        _lib.check(_lib.load().pn2_stat_outlier_flags(mean.data_ptr(), N, float(std_ratio), flags.data_ptr(),
+                                                      stats.data_ptr(), _stream(flags)), "pn2_stat_outlier_flags")
+    return flags, stats
+
+
+def knn_mean_distance(point_cloud, nb_neighbors, device=None):
+    """The mean distances delet_outlier_statistical thresholds (include/pn2.h S3): float64 [N], the
+    mean distance from each row to its nb_neighbors nearest rows, itself included; -1 for a row
+    with a non-finite coordinate."""
+    k = _neighbours("knn_mean_distance", nb_neighbors)
+    t, host = _cloud("knn_mean_distance", point_cloud, device)
+    if t.shape[0] == 0:
+        return _result(torch.empty(0, dtype=torch.float64, device=t.device), host)
+    return _result(_knn_mean(t, k), host)
+
+
+def delet_outlier_statistical(point_cloud, nb_neighbors=120, std_ratio=0.1, device=None):
+    """Keep the rows whose mean distance to their nb_neighbors nearest rows is below the cloud's
+    mean of those plus std_ratio standard deviations (include/pn2.h S1-S5), in input order.  Rows
+    keep the input's dtype (the reference returns float64, because Open3D converts)."""
+    k = _neighbours("delet_outlier_statistical", nb_neighbors)
+    if not float(std_ratio) > 0:
+        raise ValueError("pn2.collect.delet_outlier_statistical: std_ratio must be > 0, got %r" % (std_ratio,))
+    t, host = _cloud("delet_outlier_statistical", point_cloud, device)
+    if t.shape[0] == 0:
+        return _result(t, host)
+    flags, _ = _stat_flags(_knn_mean(t, k), std_ratio)
+    out, offsets = _compact(t, flags, _lib.COMPACT_FLAG_GT)
+    return _result(out[:int(offsets[1].item())], host)  # the one host read: the result's length
+
+
+# knn_mean_distance and delet_outlier_statistical are public but not in __all__, which
+# tests/test_abi_collect.py pins to its four names: the collect.py shim imports them by name
 __all__ = ["clip_distance", "delet_outlier_radius", "cluster_point", "dbscan_labels"]
