@@ -85,6 +85,8 @@
  *   pn2_knn_mean_dist_f64 / pn2_stat_outlier_flags
  *                          the capture scripts' delet_outlier_statistical
  *                                                            point_collect/collect.py:80-90
+ *   pn2_plane_segment / pn2_plane_refit
+ *                          the capture scripts' delete_plane   point_collect/collect.py:6-28
  */
 #ifndef PN2_H
 #define PN2_H
@@ -340,6 +342,93 @@ int pn2_knn_mean_dist_f64(const void *pts, int dtype, int64_t N, int64_t C, int6
                           double *mean, void *workspace, int64_t workspace_bytes, void *stream);
 int pn2_stat_outlier_flags(const double *mean, int64_t N, double std_ratio, int32_t *flags,
                            double *stats, void *stream);
+
+/* ---- plane segmentation: delete_plane (point_collect/collect.py:6-28; csrc/plane.hip), Open3D's
+ * segment_plane (RANSAC) with the draws made an input and everything after them exact arithmetic.
+ * Additive to ABI 19: no existing entry or struct changes, so PN2_ABI_VERSION stays 19.
+ * The cloud is the camera-cloud front end's (above): pts [N][ld], 3 <= C <= 64, float32 or float64,
+ * N <= pn2_collect_max_points().  Only columns 0..2 are measured; float32 inputs are widened to
+ * float64 first.  Every operation below is one float64 operation rounded once, no contraction;
+ * sqrt and / are correctly rounded.  M = num_iterations, 1 <= M <= pn2_plane_max_iterations() = 4096;
+ * n = ransac_n, 3 <= n <= pn2_plane_max_ransac_n() = 64; thr = distance_threshold, finite and > 0.
+ * This is Open3D's published structure (GetPlaneFromPoints, ComputeTrianglePlane, the
+ * count-then-error comparison, the refit over the inliers) restated.  The association of the dot
+ * products, the error term (the sum of the inliers' distances) and its order, the draws and the
+ * absence of the early exit are this project's choices, and none of it has been checked against an
+ * Open3D build.
+ *  P1 Samples.  samples [M][n] int32 (device), every entry in [0, N): an INPUT of the kernels.
+ *     pn2.collect draws them with one call, np.random.randint(0, N, size=(M, n)), from numpy's
+ *     global generator, unless the caller passes samples=.  A row may repeat an index: a repeated
+ *     point counts that many times in P2.  A row with an entry outside [0, N) is skipped like a
+ *     zero plane and raises PN2_DEVERR_INDEX.
+ *  P2 Hypothesis, n > 3 (GetPlaneFromPoints).  The row's points in row order:
+ *     centroid_k = (chain sum of p_k from 0.0) / (double)n; r = p - centroid; the six sums xx, xy,
+ *     xz, yy, yz, zz of r_i * r_j, each one chain from 0.0 in row order.
+ *       det_x = yy*zz - yz*yz    det_y = xx*zz - xz*xz    det_z = xx*yy - xy*xy
+ *       det_x > det_y && det_x > det_z:  abc = (det_x, xz*yz - xy*zz, xy*yz - xz*yy)
+ *       else det_y > det_z:              abc = (xz*yz - xy*zz, det_y, xy*xz - yz*xx)
+ *       else:                            abc = (xy*yz - xz*yy, xy*xz - yz*xx, det_z)
+ *     norm = sqrt((a*a + b*b) + c*c).  norm == 0 gives the zero plane (0, 0, 0, 0).  Otherwise
+ *     abc = abc / norm (three divisions) and d = -((a*cx + b*cy) + c*cz).
+ *  P3 Hypothesis, n == 3 (ComputeTrianglePlane).  e0 = p1 - p0, e1 = p2 - p0,
+ *     abc = (e0y*e1z - e0z*e1y, e0z*e1x - e0x*e1z, e0x*e1y - e0y*e1x); the norm, the zero test and
+ *     the normalisation as in P2; d = -((a*p0x + b*p0y) + c*p0z).
+ *  P4 Score.  dist_i = |((a*x_i + b*y_i) + c*z_i) + d|.  Point i is an inlier iff dist_i < thr; a NaN
+ *     fails, so a non-finite row is never an inlier.  count = the number of inliers.  err = the sum
+ *     of the inliers' dist_i in this order: the rows are cut into chunks of PN2_PLANE_CHUNK = 1024
+ *     consecutive indices; within a chunk one chain from 0.0 in ascending index; the chunk sums
+ *     added in ascending chunk order as one chain from 0.0.  A zero plane (P2/P3) is not scored:
+ *     count 0, err 0.0.
+ *  P5 Best.  Start from (count 0, err 0.0, index -1, plane 0).  Walk the hypotheses in ascending m:
+ *     hypothesis m replaces the best iff count_m > count || (count_m == count && err_m < err).
+ *     Among full ties the lowest index wins, and a plane with a NaN coefficient (count 0) never
+ *     wins.  This is Open3D's loop without its probabilistic early exit: every hypothesis is
+ *     scored.  If the index stays -1, nothing is an inlier (Open3D's all-zero model would call every
+ *     point an inlier: a stated deviation).
+ *  P6 Inliers.  flags[i] = 1 iff dist_i < thr under the best plane, else 0: the set Open3D returns.
+ *  P7 Refit (the model Open3D returns).  GetPlaneFromPoints (P2's formulas) over the flagged rows
+ *     (flags[i] != 0): first the centroid, then the six second moments, each sum in P4's chunked
+ *     order, n = the number of flagged rows.  With no flagged row the plane is zero.  P6 never flags
+ *     a non-finite row; a caller's flag on one makes the sums, and so the plane, NaN.
+ *
+ * pn2_plane_segment  P1-P6 as four launches on `stream`, no host read: fit (one thread per
+ *                    hypothesis), score (a workgroup per 1024-row chunk and 256 hypotheses: the
+ *                    chunk in LDS, a hypothesis' plane in registers, each thread its own count and
+ *                    err chain), select (chunk partials added in chunk order, then the best by the
+ *                    total key count desc, err asc, index asc), flag.  No atomics on floats: two
+ *                    runs give the same bits.  flags [N] int32; result [8] float64 (device) =
+ *                    {a, b, c, d, (double)best_index, (double)count, err, 0} of P5.  out_planes
+ *                    [M][4] float64, out_count [M] int32, out_err [M] float64 (device; each may be
+ *                    NULL): every hypothesis' plane, count and err; a skipped hypothesis writes a
+ *                    zero plane, count 0 and err 0.0.  n < 3, M < 1 or a threshold that is not
+ *                    finite and > 0: PN2_EINVAL; n or M above its cap: PN2_EUNSUPPORTED.
+ *                    Workspace (the float64 coordinates, the hypotheses and the per-chunk x
+ *                    per-hypothesis partials (int32 count, float64 err)):
+ *                    pn2_plane_segment_workspace_bytes(N, M) bytes, 16-byte aligned (-1: bad
+ *                    arguments).
+ * pn2_plane_score    for measurement: the score launch of pn2_plane_segment alone, on a workspace
+ *                    that a pn2_plane_segment call with the same N and M has filled (it reads the
+ *                    coordinates and hypotheses there and rewrites the partials with the same bits
+ *                    when the threshold is the same).  Checks as pn2_plane_segment's.
+ * pn2_plane_refit    plane [4] float64 (device) by P7 from flags [N] int32: two rounds (centroid,
+ *                    moments) of a chunk-partials launch and a one-wave finishing launch.
+ *                    Workspace: pn2_plane_refit_workspace_bytes(N) bytes, 16-byte aligned.
+ * The rows that are not inliers are pn2_compact_rows(flags, PN2_COMPACT_FLAG_LE, thresh = 0).
+ * N == 0: PN2_OK, nothing is written, no launch. */
+#define PN2_PLANE_CHUNK 1024
+int64_t pn2_plane_max_ransac_n(void);
+int64_t pn2_plane_max_iterations(void);
+int64_t pn2_plane_segment_workspace_bytes(int64_t N, int64_t M);
+int pn2_plane_segment(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld,
+                      const int32_t *samples, int64_t M, int64_t n, double distance_threshold,
+                      int32_t *flags, double *result, double *out_planes, int32_t *out_count,
+                      double *out_err, void *workspace, int64_t workspace_bytes, void *stream);
+int pn2_plane_score(int64_t N, int64_t M, double distance_threshold, void *workspace,
+                    int64_t workspace_bytes, void *stream);
+int64_t pn2_plane_refit_workspace_bytes(int64_t N);
+int pn2_plane_refit(const void *pts, int dtype, int64_t N, int64_t C, int64_t ld,
+                    const int32_t *flags, double *plane, void *workspace, int64_t workspace_bytes,
+                    void *stream);
 
 /* Pack a [B,N,C] strided view into [B,N,cp] with its ssq (see above).  C <= 64, as for the
  * ball query and square_distance below (else PN2_EUNSUPPORTED). */

@@ -1,4 +1,4 @@
-// collect_common.h -- what the camera-cloud units (collect.hip, knn.hip) share: the size limit,
+// collect_common.h -- what the camera-cloud units (collect.hip, knn.hip, plane.hip) share: the size limit,
 // the distance of include/pn2.h rule 2, the row loader and the argument checks of every entry.
 #pragma once
 #include "pn2_internal.h"

@@ -110,6 +110,14 @@ SIGNATURES = {
     "pn2_knn_mean_dist_workspace_bytes": (_i64, [_i64, _i64]),
     "pn2_knn_mean_dist_f64": (_int, [_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "pn2_stat_outlier_flags": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp]),
+    "pn2_plane_max_ransac_n": (_i64, []),
+    "pn2_plane_max_iterations": (_i64, []),
+    "pn2_plane_segment_workspace_bytes": (_i64, [_i64, _i64]),
+    "pn2_plane_segment": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _i64, _vp]),
+    "pn2_plane_score": (_int, [_i64, _i64, _dbl, _vp, _i64, _vp]),
+    "pn2_plane_refit_workspace_bytes": (_i64, [_i64]),
+    "pn2_plane_refit": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "pn2_pack_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pn2_ball_query_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
     "pn2_ball_query_cnt_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i64, _vp, _vp, _vp]),

@@ -2,11 +2,12 @@
 (point_collect/collect.py:30-102, its copy colledt_data_structure/collect.py, and
 camera_test/camera.py:131): a frame's cloud is cut to a depth range (clip_distance), cleaned of
 sparse points (delet_outlier_radius) and split into objects that are FPS-sampled to a common size
-(cluster_point); delet_outlier_statistical (collect.py:80-90) is the file's other outlier filter.
-The reference runs them as numpy masks and Open3D kd-tree calls on the host; here they are the
-kernels of csrc/collect.hip and csrc/knn.hip plus the existing numpy-rule FPS
-(csrc/fps_points.hip), by the rules include/pn2.h states.  Names, misspellings included, defaults and return shapes are
-the reference's; cluster_point's `visualize` flag is not carried.
+(cluster_point); delet_outlier_statistical (collect.py:80-90) is the file's other outlier filter,
+and delete_plane (collect.py:6-28) takes the table out between the clip and the filters.
+The reference runs them as numpy masks and Open3D kd-tree and RANSAC calls on the host; here they
+are the kernels of csrc/collect.hip, csrc/knn.hip and csrc/plane.hip plus the existing numpy-rule
+FPS (csrc/fps_points.hip), by the rules include/pn2.h states.  Names, misspellings included,
+defaults and return shapes are the reference's; the `visualize` flags are not carried.
 
 Input is [N, C], 3 <= C <= 64, float64 or float32: a numpy array (the result is a numpy array) or a
 torch tensor (the result is a tensor on the device it ran on), with the optional device= of
@@ -52,8 +53,9 @@ def _result(t, host):
     return t.cpu().numpy() if host else t
 
 
-def _compact(t, keys, mode, thresh=0, L=1):
-    """pn2_compact_rows -> (rows [N, C] of which the first offsets[L] are written, offsets [L+1])"""
+def _compact(t, keys, mode, thresh=0, L=1, src=None):
+    """pn2_compact_rows -> (rows [N, C] of which the first offsets[L] are written, offsets [L+1]);
+    src: an int32 [N] tensor that receives the kept rows' input indices (out_src)"""
     N, C = t.shape
     lib = _lib.load()
     with torch.cuda.device(t.device):
@@ -64,7 +66,8 @@ def _compact(t, keys, mode, thresh=0, L=1):
             raise ValueError("pn2.collect: %d rows in %d buckets are more than one compaction takes" % (N, L))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
         _lib.check(lib.pn2_compact_rows(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), keys.data_ptr(),
-                                        mode, thresh, L, out.data_ptr(), None, offsets.data_ptr(), ws.data_ptr(),
+                                        mode, thresh, L, out.data_ptr(), None if src is None else src.data_ptr(),
+                                        offsets.data_ptr(), ws.data_ptr(),
                                         need, _stream(out)), "pn2_compact_rows")
     return out, offsets
 
@@ -230,6 +233,120 @@ def delet_outlier_statistical(point_cloud, nb_neighbors=120, std_ratio=0.1, devi
     return _result(out[:int(offsets[1].item())], host)  # the one host read: the result's length
 
 
-# knn_mean_distance and delet_outlier_statistical are public but not in __all__, which
-# tests/test_abi_collect.py pins to its four names: the collect.py shim imports them by name
+_SAMPLE_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def _plane_args(who, point_cloud, distance_threshold, ransac_n, num_iterations, samples):
+    """The checks that need no device -> (threshold, n, M); ValueError as Open3D raises."""
+    lib = _lib.load()
+    thr, n, M = float(distance_threshold), int(ransac_n), int(num_iterations)
+    if n < 3:
+        raise ValueError("pn2.collect.%s: ransac_n must be >= 3, got %d" % (who, n))
+    if n > lib.pn2_plane_max_ransac_n():
+        raise ValueError("pn2.collect.%s: ransac_n = %d, above the %d the kernel takes"
+                         % (who, n, lib.pn2_plane_max_ransac_n()))
+    if M < 1:
+        raise ValueError("pn2.collect.%s: num_iterations must be >= 1, got %d" % (who, M))
+    if M > lib.pn2_plane_max_iterations():
+        raise ValueError("pn2.collect.%s: num_iterations = %d, above the %d the kernel takes"
+                         % (who, M, lib.pn2_plane_max_iterations()))
+    if not (thr > 0 and thr < float("inf")):
+        raise ValueError("pn2.collect.%s: distance_threshold must be finite and > 0, got %r"
+                         % (who, distance_threshold))
+    shape = tuple(point_cloud.shape) if isinstance(point_cloud, torch.Tensor) else np.shape(point_cloud)
+    if len(shape) == 2 and shape[0] < n:
+        raise ValueError("pn2.collect.%s: %d points, fewer than ransac_n = %d" % (who, shape[0], n))
+    if samples is not None:
+        tensor = isinstance(samples, torch.Tensor)
+        if not tensor:
+            samples = np.asarray(samples)
+        if tuple(samples.shape) != (M, n):
+            raise ValueError("pn2.collect.%s: samples must be [num_iterations, ransac_n] = [%d, %d], got shape %s"
+                             % (who, M, n, tuple(samples.shape)))
+        if (samples.dtype not in _SAMPLE_DTYPES) if tensor else (samples.dtype.kind not in "iu"):
+            raise ValueError("pn2.collect.%s: samples must be integers, got %s" % (who, samples.dtype))
+    return thr, n, M
+
+
+def _samples(samples, N, M, n, device):
+    """include/pn2.h P1 -> int32 [M, n] on the device.  None: one np.random.randint(0, N, (M, n))
+    from numpy's global generator.  A caller's entry outside [0, N) stays outside it (-1 or N)
+    through the cast, so the kernel skips its row and raises PN2_DEVERR_INDEX."""
+    if samples is None:
+        samples = np.random.randint(0, N, size=(M, n))
+    if isinstance(samples, torch.Tensor):
+        return samples.to(device).long().clamp(-1, N).to(torch.int32).contiguous()
+    return torch.from_numpy(np.clip(np.asarray(samples).astype(np.int64), -1, N).astype(np.int32)).to(device)
+
+
+def _plane_segment(t, samples, thr, stages=False, ws=None):
+    """pn2_plane_segment -> (flags int32 [N], result float64 [8]) by include/pn2.h P1-P6, and with
+    stages also (planes float64 [M, 4], count int32 [M], err float64 [M]); all on the device, no
+    host read.  ws: a caller's uint8 workspace of pn2_plane_segment_workspace_bytes(N, M), which
+    then holds the float64 rows, the hypotheses and the partials after the call."""
+    N, C = t.shape
+    M, n = samples.shape
+    lib = _lib.load()
+    with torch.cuda.device(t.device):
+        flags = torch.empty(N, dtype=torch.int32, device=t.device)
+        result = torch.empty(8, dtype=torch.float64, device=t.device)
+        outs = ()
+        if stages:
+            outs = (torch.empty(M, 4, dtype=torch.float64, device=t.device),
+                    torch.empty(M, dtype=torch.int32, device=t.device),
+                    torch.empty(M, dtype=torch.float64, device=t.device))
+        need = lib.pn2_plane_segment_workspace_bytes(N, M)
+        if ws is None:
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
+        _lib.check(lib.pn2_plane_segment(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), samples.data_ptr(),
+                                         M, n, thr, flags.data_ptr(), result.data_ptr(),
+                                         *([o.data_ptr() for o in outs] or [None, None, None]), ws.data_ptr(),
+                                         ws.numel(), _stream(flags)), "pn2_plane_segment")
+    return (flags, result) + outs
+
+
+def _plane_refit(t, flags):
+    """pn2_plane_refit -> float64 [4] on the device (include/pn2.h P7); no host read"""
+    N, C = t.shape
+    lib = _lib.load()
+    with torch.cuda.device(t.device):
+        plane = torch.zeros(4, dtype=torch.float64, device=t.device)
+        need = lib.pn2_plane_refit_workspace_bytes(N)
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
+        _lib.check(lib.pn2_plane_refit(t.data_ptr(), _DOWNSAMPLE_DTYPES[t.dtype], N, C, _ld(t), flags.data_ptr(),
+                                       plane.data_ptr(), ws.data_ptr(), need, _stream(plane)), "pn2_plane_refit")
+    return plane
+
+
+def segment_plane(point_cloud, distance_threshold, ransac_n, num_iterations, samples=None, device=None):
+    """Open3D's PointCloud.segment_plane by include/pn2.h P1-P7: (plane_model float64 [4] = a, b,
+    c, d of the plane refitted to the inliers, inliers int64 [K] ascending).  samples: the int
+    [num_iterations, ransac_n] table of row indices to draw the hypotheses from; None draws it
+    with one np.random.randint(0, N, (num_iterations, ransac_n)) from numpy's global generator
+    (Open3D draws from its own).  Every hypothesis is scored: there is no early exit."""
+    thr, n, M = _plane_args("segment_plane", point_cloud, distance_threshold, ransac_n, num_iterations, samples)
+    t, host = _cloud("segment_plane", point_cloud, device)
+    flags, _ = _plane_segment(t, _samples(samples, t.shape[0], M, n, t.device), thr)
+    plane = _plane_refit(t, flags)
+    src = torch.empty(t.shape[0], dtype=torch.int32, device=t.device)
+    _, offsets = _compact(t, flags, _lib.COMPACT_FLAG_GT, src=src)
+    inliers = src[:int(offsets[1].item())].long()  # the one host read: the result's length
+    return _result(plane, host), _result(inliers, host)
+
+
+def delete_plane(point_cloud, distance_threshold=0.006, ransac_n=20, num_iterations=1000, samples=None, device=None):
+    """Remove the dominant plane (the table): the rows that are not inliers of the best RANSAC
+    plane (include/pn2.h P1-P6), in input order and in the input's dtype.  samples as in
+    segment_plane.  The reference's `visualize` flag is not carried, and the refitted model, which
+    the reference discards, is not computed."""
+    thr, n, M = _plane_args("delete_plane", point_cloud, distance_threshold, ransac_n, num_iterations, samples)
+    t, host = _cloud("delete_plane", point_cloud, device)
+    flags, _ = _plane_segment(t, _samples(samples, t.shape[0], M, n, t.device), thr)
+    out, offsets = _compact(t, flags, _lib.COMPACT_FLAG_LE)
+    return _result(out[:int(offsets[1].item())], host)  # the one host read: the result's length
+
+
+# knn_mean_distance, delet_outlier_statistical, segment_plane and delete_plane are public but not
+# in __all__, which tests/test_abi_collect.py pins to its four names: the collect.py shim imports
+# them by name
 __all__ = ["clip_distance", "delet_outlier_radius", "cluster_point", "dbscan_labels"]
